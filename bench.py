@@ -179,7 +179,13 @@ def main():
                     help="auto: `elprep filter` (one context) when started as a plain process, the `elprep sfm` step (contig-group splits + spread split, "
                          "all-reduce) whenever started under torch.distributed.run - also with ONE rank, so that a scaling curve's N = 1 point runs the "
                          "same code as its N > 1 points")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (duplicate flags, sort permutation, duplication counters, "
+                         "BQSR tables, recalibrated QUAL) as DIR/<name>.npy, float32 / float64, at most 64 MB in all: a larger output is a fixed "
+                         "seeded sample of its elements")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -274,6 +280,7 @@ def main():
 
     host_parts = []  # per step: [tables to the host, FinalizeBQSRTables, LUT rows, LUT upload] in ms (ELP_BENCH_HOST_PARTS=1 prints them per side run)
     host_ms, wait_ms = [], []  # per step: the host's FinalizeBQSRTables + LUT (ms), and the part of it the device's sort + metrics did not hide
+    last_ctr = [None]  # the duplication counters of the last step (--dump-outputs)
 
     def make_filter_steps(eng, lut_buf):
         """the step functions of one `elprep filter` context.  Order of events as in the reference (cmd/filter.go:142-211): MarkDuplicates
@@ -319,7 +326,7 @@ def main():
                 wait_ms.append(0.0)
                 eng.apply_bqsr(None, None, MAX_CYCLE, fetch=False)
                 st.result()
-                mx.result()
+                last_ctr[0] = mx.result()
                 eng.sync()
                 return
             eng.recalibrate_device(MAX_CYCLE)
@@ -330,12 +337,12 @@ def main():
             fin = host_pool.submit(finalize_lut)
             if order == "serial":
                 eng.sort_coordinate(fetch=False)
-                eng.dup_metrics(100)
+                last_ctr[0] = eng.dup_metrics(100)
             else:
                 # the duplication-metrics pass on its side lane, driven by a second host thread while this one drives the sort
                 mx = metrics_pool.submit(eng.dup_metrics, 100)
                 eng.sort_coordinate(fetch=False)
-                mx.result()
+                last_ctr[0] = mx.result()
             t_dev = time.perf_counter()
             fin.result()
             wait_ms.append((time.perf_counter() - t_dev) * 1e3)  # what the device's sort + metrics did not hide of the host's finalisation
@@ -476,7 +483,7 @@ def main():
         def step():
             # same shape as the filter step: the host finalises the all-reduced tables (and uploads the LUT to both contexts) while the
             # GPU sorts the rank's splits
-            rk.step(MAX_CYCLE, 100, host_pool, finalize_lut, None if os.environ.get("ELP_SFM_DENSE_TABLES") else finalize_lut_rows)
+            last_ctr[0] = rk.step(MAX_CYCLE, 100, host_pool, finalize_lut, None if os.environ.get("ELP_SFM_DENSE_TABLES") else finalize_lut_rows)
             rk.sync()
         mode = "sfm"
         counts = [torch.zeros(1, dtype=torch.int64, device=cdev) for _ in range(world)]
@@ -485,6 +492,15 @@ def main():
     gen_s = time.time() - t0 - stage_s - route_s
 
     elapsed, prof = timed(step, restore, args.steps, args.warmup, prof_eng, barrier)
+    if args.dump_outputs:
+        # read back before anything else runs on the contexts: the device holds what the last timed step left there
+        if sfm_mode:
+            # every rank its own files: its group splits' context (with the all-reduced tables) and its spread split's context
+            # (the tables are on the device unless the collective is torch.distributed's: then the step reduced host copies)
+            arrays = path_outputs(rk.engines[0], last_ctr[0], rk.collective != "torch") + [("spread_" + k, a, t) for k, a, t in path_outputs(rk.engines[1], None, False)]
+            dump_outputs(args.dump_outputs, arrays, DUMP_BYTES // world, "" if world == 1 else f"rank{rank}_")
+        else:
+            dump_outputs(args.dump_outputs, path_outputs(eng, last_ctr[0], True), DUMP_BYTES)
 
     if sfm_mode:
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -819,6 +835,37 @@ def pcie_inclusive(cfg, hdr, n_reads, ms_per_step, n_main):
     L.elp_pinned_free(ptr)
     L.elp_pinned_free(out_ptr)
     return res
+
+
+DUMP_BYTES = 64_000_000 - 64 * 1024  # --dump-outputs: 64 MB in all, the .npy headers included
+
+
+def path_outputs(eng, ctr, tables: bool):
+    """what a caller of the step receives from one context, as (name, array, float dtype that holds it exactly)"""
+    out = [("flags", eng.flags(), np.float32), ("permutation", eng.permutation(), np.float64)]
+    if ctr is not None:
+        out.append(("dup_counters", np.asarray(ctr), np.float64))
+    if tables:
+        qt, ct, xt = eng.tables_fetch()
+        out += [("qual_table", qt, np.float64), ("cycle_table", ct, np.float64), ("context_table", xt, np.float64)]
+    return out + [("qual", eng.qual(), np.float32)]
+
+
+def dump_outputs(out_dir: str, arrays, budget: int, prefix: str = ""):
+    """--dump-outputs: every array as out_dir/<prefix><name>.npy in its float dtype, within `budget` bytes.  The smaller arrays are written
+    whole; an array over its share of what is left is replaced by a fixed sample of its flattened elements (seed 0, in index order) - the
+    same elements in every run with the same arguments"""
+    os.makedirs(out_dir, exist_ok=True)
+    left = budget
+    arrays = sorted(arrays, key=lambda t: t[1].size * np.dtype(t[2]).itemsize)
+    for i, (name, a, dt) in enumerate(arrays):
+        keep = min(a.size, (left // (len(arrays) - i)) // np.dtype(dt).itemsize)
+        if keep < a.size:
+            idx = np.random.default_rng(0).choice(a.size, keep, replace=False)
+            idx.sort()
+            a = np.ascontiguousarray(a).reshape(-1)[idx]
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.asarray(a).astype(dt))
+        left -= keep * np.dtype(dt).itemsize
 
 
 def flatten_sites(raw: np.ndarray) -> np.ndarray:

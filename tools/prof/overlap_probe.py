@@ -1,5 +1,5 @@
 import sys, os, time, threading
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 from elprep_amd.engine import Engine
 from tools import synth
