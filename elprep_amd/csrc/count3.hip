@@ -223,14 +223,20 @@ struct Count3 {
     // the base lies in a known site (k_ref_mark_sites, bqsr.hip)
     uint32_t R_lo = 0, R_hi = 0, k_lo = 0, k_hi = 0;
     const bool one_run = !OTHER || !(fl & (RC_MULTI | RC_GENERAL));
+    const bool skipcol = OTHER && (fl & RC_SKIPCOL);
     if (one_run) {
       const uint32_t sh = (fl & RC_PAR) ? 4u : 0u;
       R_lo = __builtin_amdgcn_alignbit(d.w03.w, d.w03.z, sh);
       R_hi = __builtin_amdgcn_alignbit(d.w45.x, d.w03.w, sh);
-      k_lo = (R_lo >> 2) & N1;
-      k_hi = (R_hi >> 2) & N1;
+      // a read with its bits in the skip column takes them from there ONLY: one run of matches can still hold a D (zero-length, or a
+      // trailing one that no clip removed), and the reference's read coordinate of a site that ends just before a D is one base short
+      // (utils.go:306-316) - the window's flags would add the base the site covers (18M0I8X47=0D47=12=19= lost base 73)
+      if (!skipcol) {
+        k_lo = (R_lo >> 2) & N1;
+        k_hi = (R_hi >> 2) & N1;
+      }
     }
-    if (OTHER && (fl & RC_SKIPCOL)) {  // known-site bits from the skip column -> nibble flags (LDS table: bit i of a byte -> bit 4 i)
+    if (skipcol) {  // known-site bits from the skip column -> nibble flags (LDS table: bit i of a byte -> bit 4 i)
       const uint32_t sk = d.skipw >> qlow;
       k_lo |= lds_read_u32(spread_at + ((sk & 0xFFu) << 2));
       k_hi |= lds_read_u32(spread_at + ((sk >> 6) & 0x3FCu));

@@ -987,37 +987,113 @@ def _c_clip(rec):
 
 
 
+def _draw_all_ops(rng, m_hi=12, n_hi=200_000):
+    """A CIGAR over all nine operations, as [(length, op)]: [H] [S] [I|D] run (sep run)* [I|D] [S] [H], where a run is one to three
+    adjacent M / = / X runs and a separator is I, D, N (1 to n_hi, log-uniform), I next to D either way, P, or a zero-length M / I / D / P;
+    sometimes a P (zero-length too) between two other ops.  Leading and trailing I / D are what aligners do not write but BAM allows."""
+    def ln(lo, hi):
+        return int(rng.integers(lo, hi + 1))
+
+    def run():
+        return [(ln(1, m_hi), "M=X"[int(rng.integers(0, 3))]) for _ in range(ln(1, 3))]
+
+    ops = []
+    if rng.random() < 0.15:
+        ops.append((ln(1, 3), "H"))
+    if rng.random() < 0.3:
+        ops.append((ln(1, 5), "S"))
+    if rng.random() < 0.12:
+        ops.append((ln(1, 3), "ID"[int(rng.integers(0, 2))]))
+    ops += run()
+    for _ in range(ln(0, 3)):
+        k = int(rng.integers(0, 8))
+        if k == 0:
+            ops.append((ln(1, 3), "I"))
+        elif k == 1:
+            ops.append((ln(1, 4), "D"))
+        elif k == 2:
+            ops.append((max(1, min(n_hi, int(np.exp(rng.uniform(0, np.log(n_hi)))))), "N"))
+        elif k == 3:
+            ops += [(ln(1, 3), "I"), (ln(1, 4), "D")]
+        elif k == 4:
+            ops += [(ln(1, 4), "D"), (ln(1, 3), "I")]
+        elif k == 5:
+            ops.append((ln(1, 3), "P"))
+        else:
+            ops.append((0, "MIDP"[int(rng.integers(0, 4))]))
+        ops += run()
+    if rng.random() < 0.12:
+        ops.append((ln(1, 3), "ID"[int(rng.integers(0, 2))]))
+    if rng.random() < 0.3:
+        ops.append((ln(1, 5), "S"))
+    if rng.random() < 0.15:
+        ops.append((ln(1, 3), "H"))
+    if rng.random() < 0.2 and len(ops) > 1:
+        k = int(rng.integers(1, len(ops)))
+        ops.insert(k, (ln(0, 2), "P"))
+    return ops
+
+
+
 def test_clipping_chain_against_a_second_restatement():  # filters/utils.go:149-262 (adaptor), 267-349 (read coordinate), 374-512 (hard clip)
     """hardClipAdaptorSequence + hardClipSoftClippedBases written a second time in Python (computeReadCoordinateForReferenceCoordinate,
     getReadCoordinateForReferenceCoordinate, hardClipCigar, cleanHardClippedCigar, hardClip with the POS shift), on random CIGARs
     with clips, insertions and deletions and random mate geometry: base window, new POS and new CIGAR must be the oracle's; where the
-    reference would panic the oracle must say so."""
+    reference would panic the oracle must say so.  The first 1500 CIGARs are M / I / D / S / H only; the next 3000 come from
+    _draw_all_ops (=, X, P, N up to 200 kb, zero-length ops, leading / trailing I or D, I next to D), with the adaptor boundary put on
+    or next to an op edge half the time (the falls-inside / ends-just-before rule for D and N)."""
     rng = np.random.default_rng(77)
     Panic = _ClipPanic
     clip = _c_clip
     checked = panics = 0
-    for trial in range(1500):
-        ops = []
-        if rng.random() < 0.15:
-            ops.append((int(rng.integers(1, 4)), "H"))
-        if rng.random() < 0.35:
-            ops.append((int(rng.integers(1, 6)), "S"))
-        ops.append((int(rng.integers(2, 12)), "M"))
-        for _ in range(int(rng.integers(0, 3))):
-            ops.append((int(rng.integers(1, 4)), "ID"[rng.integers(0, 2)]))
-            ops.append((int(rng.integers(1, 10)), "M"))
-        if rng.random() < 0.35:
-            ops.append((int(rng.integers(1, 6)), "S"))
-        if rng.random() < 0.15:
-            ops.append((int(rng.integers(1, 4)), "H"))
-        L = sum(l for l, o in ops if o in _READ)
-        span = sum(l for l, o in ops if o in _REF)
-        pos = int(rng.integers(50, 100))
-        revd = rng.random() < 0.5
-        paired = rng.random() < 0.8
-        flag = (0x1 | (0x40 if rng.random() < 0.5 else 0x80) | (0x20 if not revd else 0) if paired else 0) | (0x10 if revd else 0)
-        pnext = int(rng.integers(pos - 10, pos + span + 10))
-        tlen = int(rng.integers(-40, 41))
+    seen, new_panics = {op: 0 for op in "MIDNSHP=X"}, 0
+    for trial in range(4500):
+        if trial >= 1500:
+            ops = _draw_all_ops(rng)
+            L = sum(l for l, o in ops if o in _READ)
+            if L == 0:
+                continue
+            span = sum(l for l, o in ops if o in _REF)
+            pos = int(rng.integers(50, 100))
+            revd = rng.random() < 0.5
+            paired = rng.random() < 0.85
+            flag = (0x1 | (0x40 if rng.random() < 0.5 else 0x80) | (0x20 if not revd else 0) if paired else 0) | (0x10 if revd else 0)
+            if rng.random() < 0.5:  # a boundary on an op edge (or one off it)
+                edges, r = [pos], pos
+                for l, o in ops:
+                    if o in _REF:
+                        r += l
+                        edges.append(r)
+                t = edges[int(rng.integers(0, len(edges)))] + int(rng.integers(-1, 2))
+            else:
+                t = int(rng.integers(pos - 10, pos + span + 10))
+            if revd:
+                pnext, tlen = t + 1, -int(rng.integers(1, span + 40))
+            else:
+                pnext = int(rng.integers(pos - 10, pos + 10))
+                tlen = (t - pos) * (1 if rng.random() < 0.7 else -1)
+        else:
+            ops = []
+            if rng.random() < 0.15:
+                ops.append((int(rng.integers(1, 4)), "H"))
+            if rng.random() < 0.35:
+                ops.append((int(rng.integers(1, 6)), "S"))
+            ops.append((int(rng.integers(2, 12)), "M"))
+            for _ in range(int(rng.integers(0, 3))):
+                ops.append((int(rng.integers(1, 4)), "ID"[rng.integers(0, 2)]))
+                ops.append((int(rng.integers(1, 10)), "M"))
+            if rng.random() < 0.35:
+                ops.append((int(rng.integers(1, 6)), "S"))
+            if rng.random() < 0.15:
+                ops.append((int(rng.integers(1, 4)), "H"))
+            L = sum(l for l, o in ops if o in _READ)
+            span = sum(l for l, o in ops if o in _REF)
+            pos = int(rng.integers(50, 100))
+            revd = rng.random() < 0.5
+            paired = rng.random() < 0.8
+            flag = (0x1 | (0x40 if rng.random() < 0.5 else 0x80) | (0x20 if not revd else 0) if paired else 0) | (0x10 if revd else 0)
+            pnext = int(rng.integers(pos - 10, pos + span + 10))
+            tlen = int(rng.integers(-40, 41))
         rec = dict(ops=ops, L=L, pos=pos, flag=flag, pnext=pnext, tlen=tlen, next_refid=0)
         b = batch_from_records([dict(qname="q", flag=flag, refid=0, pos=pos, cigar="".join("%d%s" % x for x in ops), mapq=60, next_refid=0, pnext=pnext,
                                      tlen=tlen, seq="A" * L, qual=[30] * L, rgid=0)])
@@ -1027,6 +1103,7 @@ def test_clipping_chain_against_a_second_restatement():  # filters/utils.go:149-
             with pytest.raises(RuntimeError):
                 orc.clip_for_bqsr(b, 0)
             panics += 1
+            new_panics += trial >= 1500
             continue
         a, e, npos, cg = orc.clip_for_bqsr(b, 0)
         got = (a, e, npos, [("MIDNSHP=X"[int(c) & 15], int(c) >> 4) for c in cg])
@@ -1035,30 +1112,91 @@ def test_clipping_chain_against_a_second_restatement():  # filters/utils.go:149-
         else:
             assert got == (st["a"], st["a"] + st["n"], st["pos"], st["cig"]), (trial, ops, flag, pnext, tlen, got, st)
         checked += 1
-    assert checked > 1200
+        if trial >= 1500:
+            for l, o in ops:
+                seen[o] += 1
+            seen["0"] = seen.get("0", 0) + any(l == 0 for l, o in ops)
+            seen["N>=1e4"] = seen.get("N>=1e4", 0) + any(o == "N" and l >= 10_000 for l, o in ops)
+            seen["lead I/D"] = seen.get("lead I/D", 0) + (next(o for l, o in ops if o not in "HS") in "ID")
+            seen["ID adjacent"] = seen.get("ID adjacent", 0) + any(ops[k][1] + ops[k + 1][1] in ("ID", "DI") for k in range(len(ops) - 1))
+            seen["N clipped"] = seen.get("N clipped", 0) + (any(o == "N" for l, o in ops) and st["n"] not in (0, L))
+    assert checked > 1200 + 2400
+    assert all(v >= 50 for v in seen.values()), seen
+    assert new_panics > 0, "no CIGAR of the nine-op draw reached a reference panic"
 
 
 def test_bqsr_gather_against_a_full_second_restatement():  # filters/bqsr.go:225-551 + the clipping chain above
     """Recalibrate as a whole, written a second time in Python: recalibrateAln, adaptor and soft-clip hard clipping, the skip slice
     from the known sites (read coordinates by the 'left' rule on the clipped CIGAR), SNP events over the clipped CIGAR, cycle and
-    context on the clipped read - on a synthetic batch with indels, clips, adaptor read-through, supplementary records, duplicates."""
+    context on the clipped read - on a synthetic batch with indels, clips, adaptor read-through, supplementary records, duplicates, and
+    1500 more reads with _draw_all_ops CIGARs (=, X, P, N, zero-length ops, leading / trailing I or D): the bases under = and X are
+    drawn apart from the letter (X over a matching base, = over a mismatch), the N reads must be drawn and left out."""
     from tests.common import dataset
-    from elprep_amd.batch import NIL16
-    cfg, b, h, refs, sites = dataset("tiny", 2500, 7, 0.03)
+    from elprep_amd.batch import NIL16, Batch
+    cfg, b0, h, refs, sites = dataset("tiny", 2500, 7, 0.03)
+    rng = np.random.default_rng(78)
+    extra = []
+    while len(extra) < 1500:
+        ops = _draw_all_ops(rng, m_hi=40, n_hi=20_000)
+        L = sum(l for l, o in ops if o in _READ)
+        span = sum(l for l, o in ops if o in _REF)
+        r = int(rng.integers(0, h.n_ref))
+        if span + 2 >= int(h.ref_len[r]):
+            continue
+        pos = int(rng.integers(1, int(h.ref_len[r]) - span))
+        revd = rng.random() < 0.5
+        flag = 0x1 | (0x40 if rng.random() < 0.5 else 0x80) | (0x10 if revd else 0x20)
+        ins = int(rng.integers(max(1, span // 2), span + 40))  # FR pairs with short inserts: adaptor clipping
+        pnext, tlen = (max(1, pos + span - ins), -ins) if revd else (pos + int(rng.integers(0, 20)), ins)
+        if not any(o == "N" for l, o in ops):
+            try:
+                _c_clip(dict(ops=ops, L=L, pos=pos, flag=flag, pnext=pnext, tlen=tlen, next_refid=r))
+            except _ClipPanic:
+                continue  # (the reference panics: tested above)
+        seq, j = [], pos - 1
+        for l, o in ops:
+            for _ in range(l if o in _READ else 0):
+                if o in "M=X" and rng.random() < 0.6:
+                    c = chr(refs[r][j]).upper()
+                    seq.append(c if c in "ACGT" else "A")
+                else:
+                    seq.append("ACGTN"[int(rng.integers(0, 5))] if rng.random() < 0.9 else "N")
+                j += o in "M=X"
+            j += l if o in "DN" else 0
+        extra.append(dict(qname="x%d" % len(extra), flag=flag, refid=r, pos=pos, mapq=60, cigar="".join("%d%s" % x for x in ops),
+                          next_refid=r, pnext=pnext, tlen=tlen, seq="".join(seq), qual=rng.choice([2, 8, 19, 30, 37], size=L), rgid=int(rng.integers(0, h.n_rg))))
+    b = Batch.concat([b0, batch_from_records(extra)])
     flags = orc.mark_duplicates(b, h)
     comp = {"A": "T", "C": "G", "G": "C", "T": "A"}
     code = {"A": 0, "C": 1, "G": 2, "T": 3}
     b2i = {ord("a"): 1, ord("A"): 1, ord("*"): 1, ord("c"): 2, ord("C"): 2, ord("g"): 3, ord("G"): 3, ord("t"): 4, ord("T"): 4}
     wq = np.zeros((h.n_cov, 94, 2), np.int64); wc = np.zeros((h.n_cov, 94, 1001, 2), np.int64); wx = np.zeros((h.n_cov, 94, 16, 2), np.int64)
-    used = clipped_reads = 0
+    used = clipped_reads = n_excluded = 0
+    seen = {k: 0 for k in ("=", "X", "P", "0", "X on a match", "= on a mismatch", "lead I/D", "ID adjacent")}
     for i in range(b.n):
         f = int(flags[i]); mq = int(b.mapq[i]); r = int(b.refid[i]); pos = int(b.pos[i])
         ops = [(int(c) >> 4, "MIDNSHP=X"[int(c) & 15]) for c in b.cigar[int(b.cigar_off[i]):int(b.cigar_off[i + 1])]]
         o = int(b.qual_off[i]); L = int(b.qual_off[i + 1]) - o
         if b.has_sr[i] or not (0 < mq < 255) or f & (0x100 | 0x400 | 0x200) or f & 0x4 or r < 0 or pos <= 0 or L == 0 or L != int(b.l_seq[i]):
             continue
-        if b.rgid[i] == NIL16 or pos > int(h.ref_len[r]) or any(op == "N" for _, op in ops) or sum(l for l, op in ops if op in _READ) != L:
+        if b.rgid[i] == NIL16 or pos > int(h.ref_len[r]) or sum(l for l, op in ops if op in _READ) != L:
             continue
+        if any(op == "N" for _, op in ops):  # cigarContainsN (bqsr.go:239)
+            n_excluded += 1
+            continue
+        if i >= b0.n:
+            seen["="] += any(op == "=" for _, op in ops); seen["X"] += any(op == "X" for _, op in ops); seen["P"] += any(op == "P" for _, op in ops)
+            seen["0"] += any(l == 0 for l, _ in ops)
+            seen["lead I/D"] += next(op for _, op in ops if op not in "HS") in "ID"
+            seen["ID adjacent"] += any(ops[k][1] + ops[k + 1][1] in ("ID", "DI") for k in range(len(ops) - 1))
+            sq, ri, rj = b.seq_of(i), 0, pos - 1
+            for l, op in ops:
+                for _ in range(l if op in "M=X" else 0):
+                    same = sq[ri] == chr(refs[r][rj]).upper() and sq[ri] in "ACGT"
+                    seen["X on a match"] += op == "X" and same
+                    seen["= on a mismatch"] += op == "=" and not same
+                    ri += 1; rj += 1
+                ri += l if op in "IS" else 0; rj += l if op in "DN" else 0
         rec = dict(ops=ops, L=L, pos=pos, flag=f, pnext=int(b.pnext[i]), tlen=int(b.tlen[i]), next_refid=int(b.next_refid[i]))
         st = _c_clip(rec)
         n, a, cig, cpos = st["n"], st["a"], st["cig"], st["pos"]
@@ -1113,6 +1251,8 @@ def test_bqsr_gather_against_a_full_second_restatement():  # filters/bqsr.go:225
                 wx[cov, q, code[prev] | (code[cur] << 2)] += (1, e)
     qt, ct, xt = orc.bqsr_gather(b, h, orc.BqsrRef(refs, sites), flags, 500)
     assert used > 3000 and clipped_reads > 100 and wq[..., 1].sum() > 1000
+    assert n_excluded > 100, "no N reads drawn and excluded"
+    assert all(v > 20 for v in seen.values()), seen
     assert np.array_equal(qt, wq)
     assert np.array_equal(ct, wc)
     assert np.array_equal(xt, wx)
