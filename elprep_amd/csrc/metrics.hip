@@ -187,7 +187,8 @@ __global__ __launch_bounds__(256) void k_opt_starts(uint32_t L, const uint32_t *
 
 struct Tile { long long t, x, y; };
 
-// computeTileInfo :50-71; *bad is set where internal.ParseInt would panic.  One pass over the name, eight bytes per load: the
+// computeTileInfo :50-71; *bad is set where internal.ParseInt would panic (strconv.ParseInt(s, 10, 64): one optional sign, one or
+// more ASCII digits - leading zeros of any length -, the value in [-2^63, 2^63 - 1]).  One pass over the name, eight bytes per load: the
 // integer value (and parse status) of fields 2..6 is kept in scalars, the field count decides at the end which three are used
 // (7 fields -> 4,5,6; 5 fields -> 2,3,4).
 // `word(k)` = bytes 8 k .. 8 k + 7 of the name
@@ -196,7 +197,7 @@ __device__ __forceinline__ Tile tile_parse(uint32_t len, bool *bad, W word) {
   long long v2 = 0, v3 = 0, v4 = 0, v5 = 0, v6 = 0;
   uint32_t badmask = 0;       // bit k: field k does not parse
   int col = 0;
-  long long x = 0;
+  unsigned long long x = 0;   // magnitude of the current field
   uint32_t ndig = 0;          // digits seen in the current field
   bool neg = false, fbad = false, first = true;
   uint64_t w = 0;
@@ -205,8 +206,8 @@ __device__ __forceinline__ Tile tile_parse(uint32_t len, bool *bad, W word) {
     if (!end && (i & 7u) == 0) w = word(i >> 3);
     const uint32_t ch = end ? (uint32_t)':' : (uint32_t)(w >> (8 * (i & 7u))) & 0xFFu;
     if (ch == ':') {
-      const bool fb = fbad || ndig == 0 || ndig > 18;
-      const long long val = neg ? -x : x;
+      const bool fb = fbad || ndig == 0 || x > (neg ? 0x8000000000000000ull : 0x7FFFFFFFFFFFFFFFull);
+      const long long val = (long long)(neg ? 0ull - x : x);
       if (col == 2) v2 = val; else if (col == 3) v3 = val; else if (col == 4) v4 = val; else if (col == 5) v5 = val; else if (col == 6) v6 = val;
       if (col >= 2 && col <= 6 && fb) badmask |= 1u << col;
       col++;
@@ -217,7 +218,8 @@ __device__ __forceinline__ Tile tile_parse(uint32_t len, bool *bad, W word) {
       } else {
         const uint32_t d = ch - (uint32_t)'0';
         if (d > 9) fbad = true;
-        else if (ndig < 19) x = x * 10 + (long long)d;
+        else if (x > 922337203685477580ull) fbad = true;  // over 2^63 already (x * 10 >= 9223372036854775810); stays bad
+        else x = x * 10 + d;
         ndig++;
       }
       first = false;
@@ -243,14 +245,15 @@ __device__ inline Tile tile_info(const uint8_t *__restrict__ q, uint32_t len, bo
   return tile_parse(len, bad, [&](uint32_t k) { return load8(q + 8 * k); });
 }
 
-struct Member { long long t, x, y; uint32_t rg_rev; };  // rg_rev = rgid << 1 | reversed
+// rg_rev = rgid << 1 | reversed; bad: the name does not parse (the reference panics if it parses it: a member of a strand list of
+// 2..OPT_LIST_CAP entries, :327-368; k_opt_eval decides)
+struct Member { long long t, x, y; uint32_t rg_rev, bad; };
 
-__device__ inline Member make_member(const MxCols &m, uint32_t read, uint32_t *err) {
+__device__ inline Member make_member(const MxCols &m, uint32_t read) {
   bool bad = false;
   const uint64_t o = m.qname_off[read];
   Tile tl = tile_info(m.qname + o, (uint32_t)(m.qname_off[read + 1] - o), &bad);
-  if (bad) atomicOr(&err[2], 1u);
-  return Member{tl.t, tl.x, tl.y, ((uint32_t)m.rgid[read] << 1) | ((m.flag[read] & F_REVERSED) ? 1u : 0u)};
+  return Member{tl.t, tl.x, tl.y, ((uint32_t)m.rgid[read] << 1) | ((m.flag[read] & F_REVERSED) ? 1u : 0u), bad ? 1u : 0u};
 }
 
 // Members of the duplicate sets are laid out group by group; this pass over the sorted list decides the slot of each member and
@@ -275,10 +278,10 @@ __global__ __launch_bounds__(256) void k_opt_slots(MxCols m, uint32_t L, const u
   }
 }
 // dense pass over the member slots: tile / x / y from the QNAME (every lane busy, unlike a pass over all records)
-__global__ __launch_bounds__(256) void k_opt_fill(MxCols m, uint32_t total, const uint32_t *__restrict__ mread, Member *__restrict__ members, uint32_t *err) {
+__global__ __launch_bounds__(256) void k_opt_fill(MxCols m, uint32_t total, const uint32_t *__restrict__ mread, Member *__restrict__ members) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= total) return;
-  members[s] = make_member(m, mread[s], err);
+  members[s] = make_member(m, mread[s]);
 }
 
 __device__ inline uint32_t uf_find(uint32_t *p, uint32_t x) {
@@ -287,12 +290,14 @@ __device__ inline uint32_t uf_find(uint32_t *p, uint32_t x) {
   while (p[x] != r) { uint32_t nx = p[x]; p[x] = r; x = nx; }
   return r;
 }
+// absInt (filters/utils.go:62) of a - b on Go's int: the difference wraps, and absInt(MinInt64) stays MinInt64 (so it is "close")
+__device__ __forceinline__ long long go_abs_diff(long long a, long long b) {
+  const unsigned long long d = (unsigned long long)a - (unsigned long long)b;
+  return (long long)((long long)d < 0 ? 0ull - d : d);
+}
 __device__ __forceinline__ bool optical_close(const Member &a, const Member &b, long long dist) {  // isOpticalDuplicate + same RG / strand list / tile
   if (a.t == -1 || b.rg_rev != a.rg_rev || b.t != a.t) return false;
-  long long dx = a.x - b.x, dy = a.y - b.y;
-  if (dx < 0) dx = -dx;
-  if (dy < 0) dy = -dy;
-  return dx <= dist && dy <= dist;
+  return go_abs_diff(a.x, b.x) <= dist && go_abs_diff(a.y, b.y) <= dist;
 }
 
 // one thread per member slot; the origin's slot evaluates its set: optical count = n - #components under the closeness relation
@@ -323,15 +328,32 @@ __global__ __launch_bounds__(128) void k_opt_eval(MxCols m, uint32_t total, cons
     // left to the cooperative kernels: note which strand lists are over the reference's cap (they count 0 and are cut to 300001
     // entries in the set-size histograms) and the capped size of the set
     const Member *g = members + b;
-    uint32_t nr = 0;
-    for (uint32_t k = 0; k < cnt; k++) nr += g[k].rg_rev & 1u;
+    uint32_t nr = 0, bad_f = 0, bad_r = 0;
+    for (uint32_t k = 0; k < cnt; k++) {
+      const uint32_t rev = g[k].rg_rev & 1u;
+      nr += rev;
+      bad_r |= g[k].bad & rev;
+      bad_f |= g[k].bad & (rev ^ 1u);
+    }
     const uint32_t nf = cnt - nr;
+    // computeTileInfo runs on every member of a list of 2..OPT_LIST_CAP entries (:327-368): a bad name there is the reference's panic
+    if ((bad_f && nf >= 2 && nf <= OPT_LIST_CAP) || (bad_r && nr >= 2 && nr <= OPT_LIST_CAP)) atomicOr(&err[2], 1u);
     linfo[b] = 1u | (nf > OPT_LIST_CAP ? 2u : 0u) | (nr > OPT_LIST_CAP ? 4u : 0u);
     lcount[b] = (nf > OPT_LIST_CAP ? OPT_LIST_CAP + 1 : nf) + (nr > OPT_LIST_CAP ? OPT_LIST_CAP + 1 : nr);
     atomicAdd(n_large, cnt);
     large = true;
   } else if (cnt >= 2) {
   const Member *g = members + b;
+  {  // lists of up to OPT_SMALL entries: a bad name in a list of two or more is the reference's panic (:327-368)
+    uint32_t nr = 0, bad_f = 0, bad_r = 0;
+    for (uint32_t k = 0; k < cnt; k++) {
+      const uint32_t rev = g[k].rg_rev & 1u, bad = g[k].bad;
+      nr += rev;
+      bad_r |= bad & rev;
+      bad_f |= bad & (rev ^ 1u);
+    }
+    if ((bad_f && cnt - nr >= 2) || (bad_r && nr >= 2)) atomicOr(&err[2], 1u);
+  }
   if (cnt == 2) {
     optical = optical_close(g[0], g[1], dist) ? 1u : 0u;
   } else if (cnt == 3) {
@@ -556,7 +578,7 @@ static int metrics_impl(elp_ctx *c, int dist, int64_t *counters_host, int64_t *h
       ELP_HIP(c, hipMemsetAsync(linfo, 0, 4 * tp * sizeof(uint32_t), st));  // linfo, lcount, setcnt
       ELP_LAUNCH(c, "mx_opt_slots", k_opt_slots, dim3(blocks_for(L, 256)), dim3(256), 0, m, L, (const uint64_t *)ks, (const uint32_t *)vs,
                  (const uint32_t *)head, (const uint32_t *)gidx, (const uint32_t *)gstart, mread, ginfo, mset);
-      ELP_LAUNCH(c, "mx_opt_fill", k_opt_fill, dim3(blocks_for(total, 256)), dim3(256), 0, m, total, (const uint32_t *)mread, members, c->err_flag.p);
+      ELP_LAUNCH(c, "mx_opt_fill", k_opt_fill, dim3(blocks_for(total, 256)), dim3(256), 0, m, total, (const uint32_t *)mread, members);
       ELP_LAUNCH(c, "mx_opt_eval", k_opt_eval, dim3(std::min(blocks_for(total, 128), 2048u)), dim3(128),
                  (size_t)(c->n_lib + 1) * (1 + (hist ? 3 * (size_t)lds_bins : 0)) * sizeof(unsigned int), m, total, (const uint2 *)ginfo,
                  (const Member *)members, parent, (long long)dist, ctr, c->err_flag.p, hist, hist_len, lds_bins, linfo, lcount, mailbox);

@@ -249,7 +249,10 @@ int elp_get_adapted(elp_ctx *ctx, int32_t *upos_out, int32_t *score_out);
  * UnmappedReads, UnpairedReadDuplicates, ReadPairDuplicates, ReadPairOpticalDuplicates; row n_lib = "Unknown Library".
  * Requires elp_mark_duplicates.  Derived float metrics (PERCENT_DUPLICATION, ESTIMATED_LIBRARY_SIZE, :527-569) and the
  * Picard text (:608-699) stay on the host.  Runs on a side lane of the context (see elp_sort_coordinate): it reads what mark duplicates
- * left and writes nothing another call reads, so it may be called from a second host thread while the context sorts or gathers. */
+ * left and writes nothing another call reads, so it may be called from a second host thread while the context sorts or gathers.
+ * QNAMEs are parsed for tile / x / y (computeTileInfo, :50-71) where the reference parses them: every member of a strand list of 2 to
+ * 300000 listed reads.  One of those whose tile / x / y field is not a strconv.ParseInt(s, 10, 64) integer fails the call with
+ * ELP_ERR_DATA (the reference panics); a bad name anywhere else is not an error. */
 #define ELP_NCTR 7
 int elp_dup_metrics(elp_ctx *ctx, int optical_pixel_distance, int64_t *counters);
 /* The same plus the three set-size histograms the reference keeps per library (duplicatesCountHistogram,

@@ -141,11 +141,18 @@ def dup_metrics(b: Batch, h: Header, perm: Optional[np.ndarray], pixel_dist: int
     return flags, ctr, hist
 
 
-def tile_info(qname: bytes):
+def tile_info_checked(qname: bytes):
+    """computeTileInfo (filters/mark-optical-duplicates.go:50-71): (tile, x, y, panics); panics is True where internal.ParseInt
+    would panic on one of the three fields (tile, x and y are then -1)"""
     t, x, y = C.c_int64(), C.c_int64(), C.c_int64()
     buf = np.frombuffer(qname, dtype=np.uint8)
-    lib().orc_tile_info(_p(buf), C.c_uint32(len(qname)), C.byref(t), C.byref(x), C.byref(y))
-    return t.value, x.value, y.value
+    bad = lib().orc_tile_info(_p(buf), C.c_uint32(len(qname)), C.byref(t), C.byref(x), C.byref(y))
+    return t.value, x.value, y.value, bool(bad)
+
+
+def tile_info(qname: bytes):
+    """(tile, x, y); -1 each for a name without tile info and for one the reference panics on (tile_info_checked tells them apart)"""
+    return tile_info_checked(qname)[:3]
 
 
 def estimate_library_size(n_pairs: int, n_unique: int) -> int:

@@ -85,7 +85,8 @@ int orc_mark_duplicates(const orc_batch *b, const orc_header *h, uint16_t *flag_
  * histograms (index clamped to hist_len-1). */
 int orc_dup_metrics(const orc_batch *b, const orc_header *h, const uint32_t *perm, int pixel_dist,
                     uint16_t *flag_out, int64_t *counters, int64_t *hist, int hist_len);
-void orc_tile_info(const uint8_t *qname, uint32_t len, int64_t *t, int64_t *x, int64_t *y);
+/* computeTileInfo: tile/x/y of a QNAME (-1 each without tile info); returns 1 where internal.ParseInt would panic */
+int orc_tile_info(const uint8_t *qname, uint32_t len, int64_t *t, int64_t *x, int64_t *y);
 int64_t orc_estimate_library_size(int64_t n_pairs, int64_t n_unique_pairs);
 
 /* ---- known sites (intervals/intervals.go) ---- */

@@ -302,25 +302,29 @@ int orc_mark_duplicates(const orc_batch *b, const orc_header *h, uint16_t *flag_
 
 /* ---------- optical duplicates ---------- */
 
-/* Go strconv.ParseInt(s, 10, 64) for the subset that does not error; returns 0 on syntax error via *ok */
+/* strconv.ParseInt(s, 10, 64) (internal/strconv.go:27): one optional sign, then one or more ASCII digits (leading zeros of any
+ * length), the value in [-2^63, 2^63 - 1].  *ok = 0 where Go returns an error (ErrSyntax or ErrRange) */
 static int64_t parse_int(const uint8_t *p, uint32_t n, int *ok) {
   *ok = 0;
-  if (n == 0) return 0;
   uint32_t i = 0;
   int neg = 0;
-  if (p[0] == '+' || p[0] == '-') { neg = p[0] == '-'; i = 1; }
+  if (n > 0 && (p[0] == '+' || p[0] == '-')) { neg = p[0] == '-'; i = 1; }
   if (i >= n) return 0;
-  int64_t v = 0;
+  uint64_t v = 0;
+  int range = 0;
   for (; i < n; i++) {
     if (p[i] < '0' || p[i] > '9') return 0;
-    v = v * 10 + (p[i] - '0');
+    const uint64_t d = (uint64_t)(p[i] - '0');
+    if (v > (UINT64_MAX - d) / 10) range = 1;  /* v * 10 + d would not fit 64 bits */
+    v = v * 10 + d;
   }
+  if (range || v > (neg ? (uint64_t)1 << 63 : ((uint64_t)1 << 63) - 1)) return 0;
   *ok = 1;
-  return neg ? -v : v;
+  return neg ? (int64_t)(0 - v) : (int64_t)v;
 }
 
-/* filters/mark-optical-duplicates.go:50-71 */
-void orc_tile_info(const uint8_t *qname, uint32_t len, int64_t *t, int64_t *x, int64_t *y) {
+/* filters/mark-optical-duplicates.go:50-71; returns 1 where internal.ParseInt would panic (tile/x/y are then -1) */
+int orc_tile_info(const uint8_t *qname, uint32_t len, int64_t *t, int64_t *x, int64_t *y) {
   uint32_t start[9], end[9];
   int ncol = 0;
   uint32_t s = 0;
@@ -334,20 +338,23 @@ void orc_tile_info(const uint8_t *qname, uint32_t len, int64_t *t, int64_t *x, i
   int a;
   if (ncol == 7) a = 4;
   else if (ncol == 5) a = 2;
-  else { *t = *x = *y = -1; return; }
+  else { *t = *x = *y = -1; return 0; }
   int ok1, ok2, ok3;
   *t = parse_int(qname + start[a], end[a] - start[a], &ok1);
   *x = parse_int(qname + start[a + 1], end[a + 1] - start[a + 1], &ok2);
   *y = parse_int(qname + start[a + 2], end[a + 2] - start[a + 2], &ok3);
-  if (!ok1 || !ok2 || !ok3) { *t = *x = *y = -1; } /* reference panics here (internal.ParseInt); treated as "no tile info" */
+  if (!ok1 || !ok2 || !ok3) { *t = *x = *y = -1; return 1; }
+  return 0;
 }
 
-typedef struct { int64_t t, x, y; uint16_t rg; } tinfo;
+typedef struct { int64_t t, x, y; uint16_t rg; uint8_t bad; } tinfo;  /* bad: computeTileInfo would panic on this name */
 
-static int64_t abs64(int64_t v) { return v < 0 ? -v : v; }
+/* absInt (filters/utils.go:62) on Go's wrapping int: absInt(MinInt64) stays MinInt64 */
+static int64_t abs_go(int64_t v) { return v < 0 ? (int64_t)(0 - (uint64_t)v) : v; }
+static int64_t sub_go(int64_t a, int64_t b) { return (int64_t)((uint64_t)a - (uint64_t)b); }
 /* filters/unpedantic.go:32-34 */
 static int optical_short(const tinfo *a, const tinfo *b, int dist) {
-  return abs64(a->x - b->x) <= dist && abs64(a->y - b->y) <= dist;
+  return abs_go(sub_go(a->x, b->x)) <= dist && abs_go(sub_go(a->y, b->y)) <= dist;
 }
 /* :82-93 */
 static int is_optical(const tinfo *a, const tinfo *b, int dist) {
@@ -387,11 +394,13 @@ static int count_with_graph(const tinfo *d, int n, int dist) {
   return n - clusters;
 }
 
-/* :327-368 */
+/* :327-368; -1 where the reference panics: computeTileInfo runs on every member of a list of 2 to 300000 entries, on none otherwise */
 static int count_from_slice(const tinfo *d, int n, int dist) {
   if (n > 300000) return 0;
-  if (n >= 4) return count_with_graph(d, n, dist);
   if (n < 2) return 0;
+  for (int i = 0; i < n; i++)
+    if (d[i].bad) return -1;
+  if (n >= 4) return count_with_graph(d, n, dist);
   int ctr = 0;
   if (is_optical(&d[0], &d[1], dist)) ctr++;
   if (n < 3) return ctr;
@@ -402,7 +411,7 @@ static int count_from_slice(const tinfo *d, int n, int dist) {
 }
 
 static void get_tinfo(const orc_batch *b, uint64_t rec, tinfo *t) {
-  orc_tile_info(b->qname + b->qname_off[rec], (uint32_t)(b->qname_off[rec + 1] - b->qname_off[rec]), &t->t, &t->x, &t->y);
+  t->bad = (uint8_t)orc_tile_info(b->qname + b->qname_off[rec], (uint32_t)(b->qname_off[rec + 1] - b->qname_off[rec]), &t->t, &t->x, &t->y);
   t->rg = b->rgid[rec];
 }
 
@@ -479,6 +488,7 @@ int orc_dup_metrics(const orc_batch *b, const orc_header *h, const uint32_t *per
     }
     int fc = count_from_slice(fw, (int)nf, pixel_dist);
     int rc2 = count_from_slice(rv, (int)nr, pixel_dist);
+    if (fc < 0 || rc2 < 0) { free(fw); free(rv); md_free(&s); return -5; } /* reference: internal.ParseInt panics (:55-61) */
     int opt = fc + rc2;
     int dupcount = (int)(nf + nr);
     int lib = s.lib_of[origin->aln1] == ORC_NIL16 ? h->n_lib : s.lib_of[origin->aln1];
@@ -748,7 +758,9 @@ int orc_dup_metrics_mt(const orc_batch *b, const orc_header *h, const uint32_t *
         }
       }
       int lib = g.lib_of[origin->aln1] == ORC_NIL16 ? h->n_lib : g.lib_of[origin->aln1];
-      opt[(size_t)sh * nl + lib] += count_from_slice(fw, (int)nf, pixel_dist) + count_from_slice(rv, (int)nr, pixel_dist);
+      const int fc = count_from_slice(fw, (int)nf, pixel_dist), rc2 = count_from_slice(rv, (int)nr, pixel_dist);
+      if (fc < 0 || rc2 < 0) { rc_all = -5; continue; } /* reference: internal.ParseInt panics (:55-61) */
+      opt[(size_t)sh * nl + lib] += fc + rc2;
     }
     free(fw); free(rv);
   }
