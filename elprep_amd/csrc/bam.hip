@@ -459,7 +459,7 @@ int elp_stage_bam(elp_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint
   hipStream_t st = c->stream;
   // pieces are committed one at a time: whatever was derived from the records staged so far is invalid from here on, also if a later
   // piece fails
-  c->adapted = c->sorted = c->marked = false;
+  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
   c->have_qual_present = false;
   c->have_snapshot = false;
   c->flat_index_n = 0;
@@ -532,7 +532,7 @@ int elp_stage_bam(elp_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint
     at_byte = p;
   }
   ELP_HIP(c, elp::stream_wait(st));
-  c->adapted = c->sorted = c->marked = false;
+  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
   c->have_qual_present = false;
   c->have_snapshot = false;
   c->flat_index_n = 0;
@@ -597,7 +597,7 @@ static BamOut bam_out_of(const elp_ctx *c) {
 int elp_emit_sorted_bam(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
   if (!c || !n_bytes_out) return ELP_ERR_ARG;
   ELP_HIP(c, hipSetDevice(c->device));
-  if (!c->sorted) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bam: call elp_sort_coordinate first");
+  if (!c->sorted) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bam: call elp_sort_coordinate or elp_sort_queryname first");
   ELP_TRY(radix_check(c));
   if (c->raw_n != c->n) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bam: records were not staged with elp_stage_bam");
   const BamOut m = bam_out_of(c);
@@ -612,7 +612,7 @@ int elp_emit_sorted_bam(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_byte
 int elp_emit_sorted_bgzf(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
   if (!c || !n_bytes_out) return ELP_ERR_ARG;
   ELP_HIP(c, hipSetDevice(c->device));
-  if (!c->sorted) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bgzf: call elp_sort_coordinate first");
+  if (!c->sorted) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bgzf: call elp_sort_coordinate or elp_sort_queryname first");
   ELP_TRY(radix_check(c));
   if (c->raw_n != c->n) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bgzf: records were not staged with elp_stage_bam");
   const BamOut m = bam_out_of(c);
@@ -635,6 +635,7 @@ __global__ __launch_bounds__(256) void k_merge_fill(uint64_t n_out, const uint32
 
 int elp_emit_merged_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
   if (!groups || !spread || groups == spread || !n_bytes_out) return ELP_ERR_ARG;
+  if (groups->sorted_qname || spread->sorted_qname) return merge_refuses_queryname(groups, "elp_emit_merged_bam");
   if (groups->raw_n != groups->n || spread->raw_n != spread->n) return set_error(groups, ELP_ERR_ARG, "elp_emit_merged_bam: records were not staged with elp_stage_bam");
   uint64_t *slots = nullptr;
   ELP_TRY(merge_spread_slots(groups, spread, &slots));  // checks: both sorted, one device

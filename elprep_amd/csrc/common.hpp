@@ -102,6 +102,7 @@ struct elp_ctx {
 
   // derived state
   bool adapted = false, sorted = false, marked = false;
+  bool sorted_qname = false;  // the permutation (sorted) is in queryname order (elp_sort_queryname, qsort.hip), not coordinate order
   bool radix_check_pending = false;  // radix passes were queued whose look-back timeout bit nobody has read yet (fetch_err)
   bool adapt_bad_qual = false;  // adapt_score met a quality > 93 in a duplicate-marking candidate
   bool adapt_pending = false;   // ... or may have: its error word (adapt_err) has not been read yet
@@ -498,6 +499,7 @@ void group_release(elp_ctx *c);
 int group_sendrecv(elp_ctx *c, int send_peer, const void *send_dev, size_t send_bytes, int recv_peer, void *recv_dev, size_t recv_bytes);  // group.hip
 int tables_written(elp_ctx *c);  // bqsr.hip: dev_tables were just written on c->stream
 int stage_reserve(elp_ctx *c, uint64_t n, uint64_t qb, uint64_t co, uint64_t sb, uint64_t lb);
+int merge_refuses_queryname(elp_ctx *groups, const char *who);  // filter.hip: ELP_ERR_UNSUPPORTED (cmd/merge.go:175-176)
 int merge_spread_slots(elp_ctx *groups, elp_ctx *spread, uint64_t **slots_out);  // filter.hip: the merge order as ranks, on the device  // grows the staged columns (ctx.hip)
 int stage_recode_seq(elp_ctx *c, uint64_t from, uint64_t bytes);
 int stage_bam_columns(elp_ctx *c, uint32_t n_rec, uint64_t piece_bytes, uint64_t raw_end, uint64_t max_raw_rec, uint16_t split_id);  // bam.hip

@@ -165,7 +165,7 @@ int fetch_err(elp_ctx *c, uint32_t *words) {
     const uint32_t w0 = words[0] & ~256u;
     ELP_HIP(c, hipMemcpyAsync(c->err_flag.p, &w0, 4, hipMemcpyHostToDevice, c->stream));
     ELP_HIP(c, elp::stream_wait(c->stream));
-    c->sorted = false;
+    c->sorted = c->sorted_qname = false;
     c->marked = false;
     return set_error(c, ELP_ERR_HIP, "radix sort: tile look-back timed out");
   }
@@ -396,7 +396,7 @@ int elp_reset(elp_ctx *c) {
   c->max_split = 0;
   c->max_qname_len = c->max_l_seq = 0;
   c->max_pos = 0;
-  c->adapted = c->sorted = c->marked = false;
+  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
   c->have_qual_present = false;
   c->have_snapshot = false;
   c->flat_index_n = 0;
@@ -483,7 +483,7 @@ int elp_stage(elp_ctx *c, const elp_batch *b) {
   c->n_sr += n_sr;
   c->max_split = max_split;
   c->max_qname_len = max_qname_len; c->max_l_seq = max_l_seq; c->max_pos = max_pos;
-  c->adapted = c->sorted = c->marked = false;
+  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
   c->have_qual_present = false;
   c->have_snapshot = false;
   c->flat_index_n = 0;
@@ -525,7 +525,7 @@ static int d2h(elp_ctx *c, void *dst, const void *src, size_t bytes) {
 
 int elp_get_permutation(elp_ctx *c, uint32_t *out) {
   if (!c || (!out && c->n)) return ELP_ERR_ARG;
-  if (!c->sorted) return set_error(c, ELP_ERR_ARG, "elp_get_permutation: call elp_sort_coordinate first");
+  if (!c->sorted) return set_error(c, ELP_ERR_ARG, "elp_get_permutation: call elp_sort_coordinate or elp_sort_queryname first");
   ELP_TRY(radix_check(c));
   return d2h(c, out, c->perm.p, c->n * sizeof(uint32_t));
 }
@@ -565,7 +565,7 @@ int elp_rollback(elp_ctx *c) {
   ELP_HIP(c, hipSetDevice(c->device));
   if (c->n) ELP_HIP(c, hipMemcpyAsync(c->flag.p, c->snap_flag.p, c->n * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->stream));
   if (c->qual_bytes) ELP_HIP(c, hipMemcpyAsync(c->qual.p, c->snap_qual.p, c->qual_bytes, hipMemcpyDeviceToDevice, c->stream));
-  c->adapted = c->sorted = c->marked = false;
+  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
   c->have_qual_present = false;
   return 0;
 }

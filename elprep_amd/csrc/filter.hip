@@ -130,9 +130,17 @@ __global__ __launch_bounds__(256) void k_perm_keys(uint64_t n_out, const uint32_
 }
 
 
+// The merge of queryname-sorted contexts: the reference panics with "Merging of files sorted by queryname not yet implemented."
+// (cmd/merge.go:175-176)
+int merge_refuses_queryname(elp_ctx *groups, const char *who) {
+  return set_error(groups, ELP_ERR_UNSUPPORTED, "%s: a context holds a queryname permutation (elp_sort_queryname); merging queryname-sorted "
+                   "files is not implemented (cmd/merge.go:175-176)", who);
+}
+
 // MergeSortedFilesSplitPerChromosome's order as ranks, on the device: slots[j] = output slot of the j-th record of `spread`'s sorted output
 // among `groups`' sorted output (scratch slot 5 of `groups`; valid until that slot is reused).  Queued on groups->stream.
 int merge_spread_slots(elp_ctx *groups, elp_ctx *spread, uint64_t **slots_out) {
+  if (groups->sorted_qname || spread->sorted_qname) return merge_refuses_queryname(groups, "elp_merge_spread");
   if (!groups->sorted || !spread->sorted) return set_error(groups, ELP_ERR_ARG, "elp_merge_spread: both contexts must be coordinate-sorted");
   if (groups->device != spread->device) return set_error(groups, ELP_ERR_ARG, "elp_merge_spread: contexts on different devices");
   ELP_HIP(groups, hipSetDevice(groups->device));
@@ -296,7 +304,7 @@ extern "C" int elp_clean_sam(elp_ctx *c, uint64_t *n_clipped_out) {
   ELP_HIP(c, hipMemcpyAsync(hr, res, 8, hipMemcpyDeviceToHost, st));
   ELP_HIP(c, elp::stream_wait(st));
   // MAPQ changed, CIGARs may: whatever was derived from them is stale
-  c->adapted = c->sorted = c->marked = false;
+  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
   if (hr[1] & 1u) return set_error(c, ELP_ERR_DATA, "Unexpected non-0 relative clipping position in CleanSam. (reference: log.Panic, filters/utils.go:93)");
   if (hr[1] & 2u) return set_error(c, ELP_ERR_UNSUPPORTED, "elp_clean_sam: a clipped CIGAR needs an operation length outside the 28 bits of a BAM CIGAR field");
   ELP_LAUNCH(c, "clean_mapq", k_clean_mapq, dim3(blocks_for(n, 256)), dim3(256), 0, n, (const uint16_t *)c->flag.p, (const uint8_t *)c->has_sr.p, c->mapq.p);
@@ -372,7 +380,7 @@ int elp_filter_records(elp_ctx *c, const elp_predicates *p, uint64_t *n_dropped_
   }
   c->n_sr += dropped;  // they leave the output like the tagged copies do
   c->n_filtered += dropped + dropped_tagged;  // state-2 records of either origin: none of them is a duplicate-marking candidate
-  c->adapted = c->sorted = c->marked = false;
+  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
   if (n_dropped_out) *n_dropped_out = dropped;
   return 0;
 }

@@ -1201,6 +1201,6 @@ extern "C" int elp_sort_ahead(elp_ctx *c, int on) {
 extern "C" int elp_sort_coordinate(elp_ctx *c) {
   if (!c) return ELP_ERR_ARG;
   ELP_HIP(c, hipSetDevice(c->device));
-  c->sorted = false;
+  c->sorted = c->sorted_qname = false;
   return elp::sort_on_side(c);
 }

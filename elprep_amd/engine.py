@@ -3,6 +3,7 @@
 `Engine` wraps one elp_ctx (one GPU).  Method names follow the reference operators they stand in for:
 
     Engine.sort_coordinate   ~ sam.By(sam.CoordinateLess).ParallelStableSort        (sam/sam-types.go:639)
+    Engine.sort_queryname    ~ sam.By(sam.QNAMELess).ParallelStableSort             (sam/filter-pipeline.go:118-122)
     Engine.mark_duplicates   ~ filters.MarkDuplicates(alsoOpticals)                 (filters/mark-duplicates.go:406)
     Engine.dup_metrics       ~ filters.MarkOpticalDuplicates(reads, pairs, dist)    (filters/mark-optical-duplicates.go:469)
     Engine.recalibrate       ~ (*BaseRecalibrator).Recalibrate(reads, maxCycle)     (filters/bqsr.go:467)
@@ -302,6 +303,11 @@ class Engine:
 
     def sort_coordinate(self, fetch: bool = True) -> Optional[np.ndarray]:
         self._check(self.L.elp_sort_coordinate(self.h))
+        return self.permutation() if fetch else None
+
+    def sort_queryname(self, fetch: bool = True) -> Optional[np.ndarray]:
+        """elp_sort_queryname: QNAME order (Go string order), ties in staging order, records that are not output behind the others"""
+        self._check(self.L.elp_sort_queryname(self.h))
         return self.permutation() if fetch else None
 
     def permutation(self) -> np.ndarray:

@@ -230,6 +230,23 @@ int elp_sort_coordinate(elp_ctx *ctx);
  * host that has work of its own between the two calls.) */
 int elp_sort_ahead(elp_ctx *ctx, int on);
 int elp_get_permutation(elp_ctx *ctx, uint32_t *perm_out /* n */);
+/* ---- queryname sort: By(QNAMELess).ParallelStableSort (sam/filter-pipeline.go:118-122, sam/sam-types.go:475-481, :639-641) ----
+ * The Finalize step of `elprep filter / sfm --sorting-order queryname` (cmd/filter.go:361,451), in place of elp_sort_coordinate.
+ * perm[k] = staging index of the record at sorted position k (elp_get_permutation).  Order: QNAME bytes as Go compares strings -
+ * unsigned bytes, lexicographic, a proper prefix first ("" < "a" < "a0" < "b"); records with equal QNAMEs keep staging order (mates and
+ * secondary / supplementary records of a template stay in arrival order).  The first elp_num_sorted() entries are the output; the
+ * records that are not output (sr-tagged copies, records rejected by elp_filter_records) follow behind them, ALSO in QNAME order with
+ * ties in staging order.  Reads the QNAME column and the record-state column only (no sort keys, no scores: nothing of
+ * elp_mark_duplicates is needed), so it may be called on its own or after elp_mark_duplicates, elp_filter_records or
+ * elp_sort_coordinate, with the same result.  The context remembers which sort made its permutation last: elp_get_permutation and
+ * elp_emit_sorted_bam / elp_emit_sorted_bgzf give that order; elp_merge_spread and elp_emit_merged_bam return ELP_ERR_UNSUPPORTED
+ * while either context holds a queryname permutation (the reference panics: "Merging of files sorted by queryname not yet
+ * implemented.", cmd/merge.go:175-176).  Key passes queued ahead for a coordinate sort (elp_sort_ahead) are left as they are.
+ * Concurrency: as elp_sort_coordinate - the sort runs on the same side lane of the context (a stream, scratch pool and error words of
+ * its own) and writes the permutation only; once elp_mark_duplicates has returned, a host may call it from a thread of its own WHILE
+ * other threads call elp_dup_metrics and drive elp_bqsr_gather(_device) -> finalize -> elp_bqsr_apply on the same context.  Calls that
+ * CHANGE staged records must not overlap with it.  Limits as for staging: 2^32-16 records, QNAMEs of at most 1000 bytes. */
+int elp_sort_queryname(elp_ctx *ctx);
 /* number of records that survive RemoveOptionalReads = staged records without the sr tag: the first elp_num_sorted() entries of
  * the permutation are the output of the run, the tagged copies follow behind them */
 uint64_t elp_num_sorted(const elp_ctx *ctx);
