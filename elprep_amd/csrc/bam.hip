@@ -548,9 +548,14 @@ static int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint
   // record is never longer than the staged one (integer fields only shrink when re-encoded) - except that elp_clean_sam may have added
   // ONE CIGAR operation (4 bytes) - so the largest staged record + 4 bounds it; BGZF framing adds 26 bytes per 65280 (< 0.1 %: the bound
   // leaves 1/64 of headroom).
-  const uint32_t CHUNK = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1u << 21, 0xFC000000ull / (std::max<uint64_t>(max_raw_rec, 64) + 4)));
+  uint32_t CHUNK = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1u << 21, 0xFC000000ull / (std::max<uint64_t>(max_raw_rec, 64) + 4)));
+  if (c->tune.emit_pass > 0) CHUNK = std::min<uint32_t>(CHUNK, (uint32_t)c->tune.emit_pass);  // (elp_set_tuning: tests)
   uint64_t total = 0;
   hipStream_t st = c->stream;
+  // BGZF: every member but the last holds 65280 bytes of the stream (bgzf.hip's BGZF_PAYLOAD), wherever the passes fall - the bytes of a
+  // pass behind its last full member are carried into the next pass and framed there (the last pass frames all it holds)
+  constexpr uint64_t BGZF_MEMBER_BYTES = 65280;
+  std::vector<uint8_t> carry, next_carry;
   for (uint64_t k0 = 0; k0 < n_out; k0 += CHUNK) {
     const uint32_t cnt = (uint32_t)std::min<uint64_t>(CHUNK, n_out - k0);
     uint32_t *sizes;
@@ -566,24 +571,33 @@ static int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint
     if (he & 16u) return set_error(c, ELP_ERR_UNSUPPORTED, "elp_emit_sorted_bam: H-typed optional field");
     if (he) return set_error(c, ELP_ERR_DATA, "elp_emit_sorted_bam: malformed optional fields");
     // (BGZF: the size of the stored form - what the pass needs room for; the compressed members are never larger, their actual size is
-    // known behind the device pass.  A size query returns this upper bound)
-    uint64_t out_bytes = bgzf ? bgzf_framed_size(chunk_bytes) : (uint64_t)chunk_bytes;
-    if (!out) { total += out_bytes; continue; }  // size query
+    // known behind the device pass.  A size query returns this upper bound: framed pass by pass it is never below the stored form of the
+    // members the carried bytes make)
+    if (!out) { total += bgzf ? bgzf_framed_size(chunk_bytes) : (uint64_t)chunk_bytes; continue; }  // size query
+    const uint64_t held = (uint64_t)carry.size(), pass_bytes = held + chunk_bytes;  // (held < 65280: the pass stays below 4 GiB, CHUNK's headroom)
+    const uint64_t frame_bytes = !bgzf || k0 + cnt >= n_out ? pass_bytes : pass_bytes / BGZF_MEMBER_BYTES * BGZF_MEMBER_BYTES;
+    uint64_t out_bytes = bgzf ? (frame_bytes ? bgzf_framed_size(frame_bytes) : 0) : (uint64_t)chunk_bytes;
     if (total + out_bytes > cap) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bam: output buffer too small (%llu bytes needed so far)", (unsigned long long)(total + out_bytes));
     uint8_t *d_out;
-    ELP_TRY(scratch(c, 5, (size_t)chunk_bytes + 64, &d_out));
+    ELP_TRY(scratch(c, 5, (size_t)pass_bytes + 64, &d_out));
+    if (held) ELP_HIP(c, hipMemcpyAsync(d_out, carry.data(), held, hipMemcpyHostToDevice, st));
     const unsigned grid = std::min<unsigned>(blocks_for((uint64_t)cnt * 64, 256), (unsigned)c->n_cu * 32);
-    ELP_LAUNCH(c, "emit_bam", k_bam_out_emit, dim3(grid), dim3(256), 0, m, m2, src, k0, cnt, (const uint32_t *)offs, d_out);
+    ELP_LAUNCH(c, "emit_bam", k_bam_out_emit, dim3(grid), dim3(256), 0, m, m2, src, k0, cnt, (const uint32_t *)offs, d_out + held);
     const uint8_t *d_send = d_out;
     if (bgzf) {
-      uint8_t *d_framed;
-      ELP_TRY(scratch(c, 7, (size_t)out_bytes + 64, &d_framed));
-      if (c->tune.bgzf_stored) ELP_TRY(bgzf_frame(c, d_out, chunk_bytes, d_framed));  // stored DEFLATE blocks (tests, measurements)
-      else ELP_TRY(bgzf_deflate(c, d_out, chunk_bytes, d_framed, &out_bytes));
+      uint8_t *d_framed = nullptr;
+      if (frame_bytes) {
+        ELP_TRY(scratch(c, 7, (size_t)out_bytes + 64, &d_framed));
+        if (c->tune.bgzf_stored) ELP_TRY(bgzf_frame(c, d_out, frame_bytes, d_framed));  // stored DEFLATE blocks (tests, measurements)
+        else ELP_TRY(bgzf_deflate(c, d_out, frame_bytes, d_framed, &out_bytes));
+      }
+      next_carry.resize(pass_bytes - frame_bytes);  // (not `carry`: its bytes may still be on their way to the device)
+      if (!next_carry.empty()) ELP_HIP(c, hipMemcpyAsync(next_carry.data(), d_out + frame_bytes, next_carry.size(), hipMemcpyDeviceToHost, st));
       d_send = d_framed;
     }
-    ELP_HIP(c, hipMemcpyAsync(out + total, d_send, out_bytes, hipMemcpyDeviceToHost, st));
+    if (out_bytes) ELP_HIP(c, hipMemcpyAsync(out + total, d_send, out_bytes, hipMemcpyDeviceToHost, st));
     ELP_HIP(c, elp::stream_wait(st));
+    carry.swap(next_carry);
     total += out_bytes;
   }
   *n_bytes_out = total;

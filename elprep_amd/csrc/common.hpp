@@ -252,6 +252,7 @@ struct elp_ctx {
     int sort_pairs = 0;        // 1: the coordinate sort moves (key, index) pairs even where key << b | index fits one word
     int tie_rounds = 0;        // 1: the sort's long runs by LSD rounds over every live position (no key-then-compare shortcut)
     int exchange_piece = 0;    // > 0: records per piece of elp_exchange_records (tests: several pieces on small inputs)
+    int emit_pass = 0;         // > 0: at most this many records per pass of the BAM / BGZF emitters (tests: several passes on small inputs)
     long long bgzf_inflate_piece = 2ll << 30;  // elp_stage_bgzf: inflated bytes whose blocks are decoded by one launch (token scratch: 2.7x that)
     int bgzf_copy_chunk = 0;   // elp_stage_bgzf: blocks per H2D chunk / decoder launch (0: what fills the chip once)
     int bgzf_tok_lds = 0;      // (experiments) unused dynamic LDS bytes per decoder wave: lowers the waves per CU

@@ -591,6 +591,7 @@ int elp_set_tuning(elp_ctx *c, const char *key, int64_t value) {
   else if (k == "radix_tile") c->tune.radix_tile = v;
   else if (k == "sort_pairs") c->tune.sort_pairs = v;
   else if (k == "exchange_piece") c->tune.exchange_piece = v;
+  else if (k == "emit_pass") c->tune.emit_pass = v;
   else if (k == "bgzf_stored") c->tune.bgzf_stored = v;
   else if (k == "bgzf_inflate") c->tune.bgzf_inflate = v;
   else if (k == "bgzf_tok_fail_above") c->tune.bgzf_tok_fail_above = v;

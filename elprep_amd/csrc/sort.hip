@@ -481,7 +481,7 @@ int adapt_scores(elp_ctx *c) {
   } else {
     ELP_HIP(c, hipMemsetAsync(c->score.p, 0, n * sizeof(int32_t), c->stream));  // (a read without bases belongs to no tile's group)
     const unsigned grid = (unsigned)std::min<uint64_t>(flat_steps<ScoreBody>(c->qual_bytes), (uint64_t)c->n_cu * 4);
-    ELP_LAUNCH(c, "adapt_score", k_score_flat, dim3(grid), dim3(FL_THREADS), 0, n, (const uint64_t *)c->qual_off.p, (const uint8_t *)c->qual.p,
+    ELP_LAUNCH(c, "adapt_score_flat", k_score_flat, dim3(grid), dim3(FL_THREADS), 0, n, (const uint64_t *)c->qual_off.p, (const uint8_t *)c->qual.p,
                c->qual_bytes, (const uint32_t *)c->tile_first.p, (const uint16_t *)c->flag.p, c->score.p, c->qbounds.p, c->adapt_err.p);
   }
   c->adapt_pending = true;
@@ -916,7 +916,10 @@ static int sort_impl(elp_ctx *c, uint64_t *presorted = nullptr /* the key passes
   const bool words = c->tune.sort_pairs != 1 && c->key_bits >= 1 && c->key_bits + idx_bits <= 64;
   if (words && presorted) ks = presorted;
   else if (words) ELP_TRY(radix_sort_fused(c, c->key.p, n, c->key_bits, idx_bits, k0, k1, &ks));
-  else ELP_TRY(radix_sort_pairs_low(c, k0, v0, k1, v1, n, (c->key_bits + 7) / 8, &ks, &vs, c->key.p, true));
+  else {
+    ProfScope ps(c, "sort_pairs_");  // (the pair form's passes are booked apart from the word form's: tests see which one ran)
+    ELP_TRY(radix_sort_pairs_low(c, k0, v0, k1, v1, n, (c->key_bits + 7) / 8, &ks, &vs, c->key.p, true));
+  }
   const SortedView sv{ks, vs, words ? (uint32_t)idx_bits : 0u};
   TieCols t{c->qname_off.p, c->qname.p, c->flag.p, c->mapq.p, c->next_refid.p, c->pnext.p, c->tlen.p};
   // run members -> compact list (the other half of `vbuf` is free: the radix sort left its result in one half); bounds of the runs

@@ -175,6 +175,39 @@ def test_emit_sorted_bgzf_inflates_to_the_record_stream():
     assert [len(m) for _, m in mem[:-1]] == [65280] * (len(mem) - 1) and len(mem) >= 3
 
 
+@pytest.mark.parametrize("per_pass,stored", [(1, 0), (333, 0), (2048, 0), (333, 1)])
+def test_emit_in_passes_keeps_bgzf_members_whole(per_pass, stored):
+    """the emitters in passes of `per_pass` records (elp_set_tuning "emit_pass"; by default a pass holds 2^21 records): the same BAM
+    bytes as one pass, and BGZF members that hold the same 65280-byte parts of the stream wherever the passes end (the stored form: the
+    same bytes; a compressed member's DEFLATE data depends on the launch that made it, so only what it inflates to is compared)"""
+    b, h, raw, rec_off = _bam_case()
+    e = Engine(h)
+    try:
+        e.set_read_group_ids(h.rg_ids)
+        e.stage_bam(raw, rec_off=rec_off)
+        e.mark_duplicates(True)
+        e.sort_coordinate()
+        e.set_tuning("bgzf_stored", stored)
+        want = e.emit_sorted_bam().tobytes()
+        want_bz = e.emit_sorted_bgzf().tobytes()
+        e.set_tuning("emit_pass", per_pass)
+        got = e.emit_sorted_bam().tobytes()
+        bz = e.emit_sorted_bgzf().tobytes()
+    finally:
+        e.set_tuning("emit_pass", 0)
+        e.set_tuning("bgzf_stored", 0)
+        e.close()
+    assert got == want
+    mem = _members(bz)
+    assert len(mem) >= 3 and b.n > 2 * per_pass  # (several members, and several passes)
+    assert b"".join(m for _, m in mem) == want
+    assert all(len(m) == 65280 for _, m in mem[:-1]) and 0 < len(mem[-1][1]) <= 65280
+    if stored:
+        assert bz == want_bz
+    else:
+        assert [m for _, m in _members(want_bz)] == [m for _, m in mem]
+
+
 def _bgzf(stream: bytes, level: int, strategy: int = 0, cut: int = 65280, mem_level: int = 8) -> bytes:
     import struct
     import zlib
