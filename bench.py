@@ -7,9 +7,13 @@ synthetic 150 bp paired-end reads (inputs are in HBM before the timed region sta
 separately and is never `value`).  Rank 0 prints ONE JSON line.
 
 N = 1 is `elprep filter` (one context): BASELINE.json's config C3 (50 M reads, sort + markdup + BQSR), the largest single-GPU
-configuration.  The same line carries, as `extra`, the other single-GPU facts asked for: config C2 (mark duplicates + sort only) on
-the same staged reads, the path on a read set with ~40 distinct quality values (the 7-value binned qualities of the main workload
-are the easy case for the BQSR kernels), and the PCIe-inclusive staging rate through elp_stage_bam.
+configuration.  A plain run does what the headline needs and no more: it stages the reads, warms up, times the steps, writes
+--dump-outputs and prints the line (with the stage / kernel times and the roofline of the timed steps' own profile).  `--full` adds
+everything else, all of it outside the timed region: the same step in serial order (`serial_order`: every kernel uncontended), as
+`extra` the other step orders, config C2 (mark duplicates + sort only) on the same staged reads, the PCIe-inclusive staging rates
+through elp_stage_bam / elp_stage_bgzf, the path on variants of the read set (~40 distinct quality values - the 7-value binned
+qualities of the main workload are the easy case for the BQSR kernels -, shuffled input, 16 / 32 read groups, one GPU's share of a
+30x WGS run on hg38), and the all-cores CPU baseline with `verify` (the device's outputs on the CPU leg's reads against the oracle's).
 
 N > 1 is `elprep sfm`: contig groups -> ranks; the only exchange per step is ONE all-reduce (RCCL through the C ABI's device
 group) of the BQSR count tables + duplication counters.  `--scaling weak` (default; per-GPU reads fixed) or `--scaling strong
@@ -168,13 +172,16 @@ def main():
     ap.add_argument("--stages", choices=["full", "c2"], default="full", help="full = BASELINE config C3 (sort+markdup+BQSR); c2 = mark duplicates + sort only")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak", help="N > 1: per-GPU reads fixed, or --total-reads partitioned by contig groups")
     ap.add_argument("--total-reads", type=int, default=0, help="strong scaling: reads of the whole job (default: --reads)")
-    ap.add_argument("--cpu-reads", type=int, default=8_000_000, help="sample size for the CPU baseline leg (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the comparison of the device path with the CPU leg's outputs (it needs the CPU leg)")
-    ap.add_argument("--no-extra", action="store_true", help="N = 1: skip the C2 / full-quality / PCIe-inclusive side measurements")
-    ap.add_argument("--extra-reads", type=int, default=16_000_000, help="reads of the full-quality side measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the timed steps, also run the serial-order steps, the side measurements (`extra`) and the CPU baseline with "
+                         "`verify` (a mismatch exits with 3); the options below trim what --full runs")
+    ap.add_argument("--cpu-reads", type=int, default=8_000_000, help="--full: sample size for the CPU baseline leg (0 = skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the comparison of the device path with the CPU leg's outputs (it needs the CPU leg)")
+    ap.add_argument("--no-extra", action="store_true", help="--full, N = 1: skip the side measurements (other orders, C2, PCIe-inclusive, read-set variants)")
+    ap.add_argument("--extra-reads", type=int, default=16_000_000, help="--full: reads of the read-set variants' side measurements")
     ap.add_argument("--c4-reads", type=int, default=int(os.environ.get("ELP_BENCH_C4_READS", 75_000_000)),
-                    help="N = 1 side measurement `c4_share`: reads on the hg38-sized genome (0 = skip)")
+                    help="--full, N = 1 side measurement `c4_share`: reads on the hg38-sized genome (0 = skip)")
     ap.add_argument("--mode", choices=["auto", "filter", "sfm"], default="auto",
                     help="auto: `elprep filter` (one context) when started as a plain process, the `elprep sfm` step (contig-group splits + spread split, "
                          "all-reduce) whenever started under torch.distributed.run - also with ONE rank, so that a scaling curve's N = 1 point runs the "
@@ -186,9 +193,6 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
-
-    import torch
-    import torch.distributed as dist
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -212,6 +216,53 @@ def main():
     if sfm_mode:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    assert args.gpus == world, f"--gpus {args.gpus} but WORLD_SIZE={world}"
+
+    from collections import deque
+    from concurrent.futures import ThreadPoolExecutor
+    from tools import synth
+
+    cfg = synth.config(args.genome)
+    cfg.qual_mode = 1 if args.quals == "full" else 0
+    hdr = cfg.header()
+    pairs_per_rank = args.reads // 2
+    workers = max(1, min(12, effective_cores() // max(world, 1)))
+    chunk = 1_000_000
+
+    def generated(jobs):
+        """the batches of `jobs` = [(config, pair_lo, pair_hi), ...], to be taken in order; the generator is deterministic per pair index,
+        so chunks are produced by a small thread pool (ctypes releases the GIL), which starts at once - before the first batch is asked for"""
+        pool = ThreadPoolExecutor(workers)
+        it = iter(jobs)
+        q = deque()
+        for _ in range(workers + 1):
+            j = next(it, None)
+            if j is not None:
+                q.append(pool.submit(synth.generate, *j))
+
+        def batches():
+            with pool:
+                while q:
+                    b = q.popleft().result()
+                    j = next(it, None)
+                    if j is not None:
+                        q.append(pool.submit(synth.generate, *j))
+                    yield b
+        return batches()
+
+    # the host's inputs are made while torch and the device come up (the generator is C on all host cores; the imports and the runtime's
+    # set-up mostly wait): `elprep filter`'s reads from here on, the reference and its known sites beside them.  The same inputs as made
+    # one after the other
+    t_gen = time.time()
+    refs_pool = ThreadPoolExecutor(1)
+    refs_fut = refs_pool.submit(lambda: [(r, synth.reference(cfg, r), flatten_sites(synth.known_sites_raw(cfg, r))) for r in range(hdr.n_ref)])
+    refs_pool.shutdown(wait=False)
+    main_batches = None if sfm_mode else generated([(cfg, lo, min(lo + chunk, pairs_per_rank)) for lo in range(0, pairs_per_rank, chunk)])
+
+    import torch
+    import torch.distributed as dist
+
+    if sfm_mode:
         if backend == "nccl":
             torch.cuda.set_device(local_rank)
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
@@ -221,23 +272,11 @@ def main():
             dist.init_process_group(backend)
     else:
         torch.cuda.set_device(0)
-    assert args.gpus == world, f"--gpus {args.gpus} but WORLD_SIZE={world}"
     dev = torch.device("cuda", local_rank if sfm_mode else 0)
     cdev = dev if (not sfm_mode or backend == "nccl") else torch.device("cpu")  # where collective buffers live
 
     from elprep_amd.engine import BqsrTables, Engine
-    from tools import synth
 
-    cfg = synth.config(args.genome)
-    cfg.qual_mode = 1 if args.quals == "full" else 0
-    hdr = cfg.header()
-    pairs_per_rank = args.reads // 2
-    refs_sites = [(r, synth.reference(cfg, r), flatten_sites(synth.known_sites_raw(cfg, r))) for r in range(hdr.n_ref)]
-
-    from collections import deque
-    from concurrent.futures import ThreadPoolExecutor
-    workers = max(1, min(12, effective_cores() // max(world, 1)))
-    chunk = 1_000_000
     host_pool = ThreadPoolExecutor(1)
     metrics_pool = ThreadPoolExecutor(1)
     sort_pool = ThreadPoolExecutor(1)
@@ -255,23 +294,6 @@ def main():
     # 1024-thread workgroups find no CU while the pair phase's and the prologues' small workgroups keep every CU partly occupied, and with
     # smaller tiles they slow the pair phase by what they gain (profiles/round6_sort_ahead_ab.txt); off unless asked for
     sort_ahead = os.environ.get("ELP_BENCH_SORT_AHEAD", "0") != "0"
-
-    def generated(jobs):
-        """yield the batches of `jobs` = [(config, pair_lo, pair_hi), ...] in order; the generator is deterministic per pair index,
-        so chunks are produced by a small thread pool (ctypes releases the GIL)"""
-        with ThreadPoolExecutor(workers) as pool:
-            q = deque()
-            it = iter(jobs)
-            for _ in range(workers + 1):
-                j = next(it, None)
-                if j is not None:
-                    q.append(pool.submit(synth.generate, *j))
-            while q:
-                b = q.popleft().result()
-                j = next(it, None)
-                if j is not None:
-                    q.append(pool.submit(synth.generate, *j))
-                yield b
 
     def barrier():
         if sfm_mode:
@@ -359,7 +381,7 @@ def main():
             eng.sync()
         return step_full, step_c2, restore
 
-    t0 = time.time()
+    t0 = t_gen if not sfm_mode else time.time()  # (filter: gen_s also holds what the imports and the device's set-up kept hidden under it)
     stage_s = 0.0
     route_s = 0.0  # sfm: classifying the generated records by split and exchanging the few that belong to another rank
     dev_id = local_rank if sfm_mode else 0
@@ -368,12 +390,13 @@ def main():
         # ---- `elprep filter`: one context holds everything (untimed staging; PCIe-inclusive rate reported separately)
         eng = Engine(hdr, dev_id)
         n_total = 0
-        for b in generated([(cfg, lo, min(lo + chunk, pairs_per_rank)) for lo in range(0, pairs_per_rank, chunk)]):
+        for b in main_batches:
             ts = time.time()
             eng.stage(b)
             stage_s += time.time() - ts
             n_total += b.n
             del b
+        refs_sites = refs_fut.result()
         for r, ref, sites in refs_sites:
             eng.set_reference(r, ref)
             eng.set_known_sites(r, sites)
@@ -450,6 +473,7 @@ def main():
             route_s += time.time() - tr
             del b
         n_total = rk.n_reads  # the tagged copies are not reads of their own
+        refs_sites = refs_fut.result()
         for r, ref, sites in refs_sites:
             rk.set_reference(r, ref)
             rk.set_known_sites(r, sites)
@@ -518,7 +542,7 @@ def main():
         conc = (not sfm_mode and args.stages == "full" and order == "three") or sfm_mode
         serial_order = None
         dom_serial = None
-        if not sfm_mode and args.stages == "full" and order != "serial":
+        if args.full and not sfm_mode and args.stages == "full" and order != "serial":
             # the same step with its stages one after the other (as until round 5), OUTSIDE the timed region: what every kernel takes when it
             # has the GPU to itself - the stage table and the dominant kernel's roofline without the other streams' kernels in its way
             el_s, prof_s = timed(lambda: step_full("serial"), restore, 3, 1, eng, barrier)
@@ -532,6 +556,9 @@ def main():
             roof["note"] = ("`achieved` / `frac`: the dominant kernel's time in the TIMED steps, where the coordinate sort and the metrics pass run at the same "
                             "time on streams of their own and take CUs, LDS and bandwidth from it; `frac_uncontended`: the same kernel, same reads, in the "
                             "serial-order steps behind the timed region (serial_order.roofline)")
+        elif not sfm_mode and conc:
+            roof["note"] = ("`kernel`, `achieved` / `frac`: the kernel with the most time in the TIMED steps, where the coordinate sort and the metrics pass "
+                            "run at the same time on streams of their own; the uncontended figures (`serial_order`) take steps of their own: --full")
         if not sfm_mode and args.stages == "full" and order == "metrics":
             roof["concurrent_streams"] = ("the duplication-metrics pass runs under the coordinate sort (side lanes of the context, two host threads): the two "
                                           "stages' kernel times are contended and their sum exceeds what they add to the step; mark duplicates, the BQSR "
@@ -585,7 +612,7 @@ def main():
             out["imbalance_max_over_mean"] = round(max(per_rank_reads) / (sum(per_rank_reads) / len(per_rank_reads)), 4)
 
     # ---- N = 1 side measurements: config C2 on the same reads, the ~40-quality read set, the PCIe-inclusive staging rate
-    if not sfm_mode and rank == 0 and not args.no_extra:
+    if args.full and not sfm_mode and rank == 0 and not args.no_extra:
         extra = {}
         try:
             if args.stages == "full":
@@ -674,7 +701,7 @@ def main():
 
     verify_failed = False
     if rank == 0:
-        if not sfm_mode and not args.no_cpu_baseline and args.cpu_reads > 0:
+        if args.full and not sfm_mode and not args.no_cpu_baseline and args.cpu_reads > 0:
             # the CPU leg: timed as the baseline, and its outputs are what the device path is checked against on the same reads
             # (outside every timed region): the bench line carries its own parity proof at the scale the oracle finishes in seconds
             if not sfm_mode and eng is not None:

@@ -45,7 +45,7 @@ def test_bench_dump_outputs_repeat(tmp_path):
     for k in range(2):
         d = tmp_path / f"run{k}"
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--reads", "300000",
-                            "--no-extra", "--c4-reads", "0", "--cpu-reads", "100000", "--dump-outputs", str(d)],
+                            "--full", "--no-extra", "--c4-reads", "0", "--cpu-reads", "100000", "--dump-outputs", str(d)],
                            cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -59,3 +59,23 @@ def test_bench_dump_outputs_repeat(tmp_path):
     n = l0["config"]["reads_per_gpu"]
     assert a["flags"].shape == (n,) and np.array_equal(np.sort(a["permutation"]), np.arange(n))
     assert a["qual_table"][..., 0].sum() > 0 and a["dup_counters"].sum() > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.fresh_only
+def test_bench_plain_run_is_the_headline_only(tmp_path):
+    """without --full the run stages, warms up, times the steps and writes its outputs: the line carries the headline fields, and none of
+    the measurements that take runs of their own (serial order, side measurements, CPU baseline, verify)"""
+    d = tmp_path / "plain"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--reads", "300000",
+                        "--dump-outputs", str(d)],
+                       cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    assert "extra" not in line and "cpu_baseline" not in line and "verify" not in line and line["serial_order"] is None
+    assert sorted(_dumped(d)) == ["context_table", "cycle_table", "dup_counters", "flags", "permutation", "qual", "qual_table"]

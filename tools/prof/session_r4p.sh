@@ -2,7 +2,7 @@
 OUT=gpurun_out/r4p; mkdir -p $OUT
 timeout 300 python -m pytest tests/test_gpu_round4.py tests/test_gpu_round3.py -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest.log
 SKIP_TESTS=1 bash tools/prof/ab_round.sh r4p 50000000 t8k t16k:ELP_TUNE=radix_tile=3
-timeout 400 python bench.py --reads 16000000 --steps 4 --warmup 1 --no-cpu-baseline > $OUT/bench16.json 2> $OUT/bench16.err; echo "b16 rc=$?"
+timeout 400 python bench.py --full --reads 16000000 --steps 4 --warmup 1 --no-cpu-baseline > $OUT/bench16.json 2> $OUT/bench16.err; echo "b16 rc=$?"
 python - <<'PY'
 import json
 d=json.load(open("gpurun_out/r4p/bench16.json"))

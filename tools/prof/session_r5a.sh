@@ -1,7 +1,7 @@
 # round-5 session a: all GPU tests (no -x: every failure is wanted), then the default bench line
 OUT=gpurun_out/r5a; mkdir -p $OUT
 timeout 600 python -m pytest tests -m gpu -q -p no:cacheprovider > $OUT/pytest.log 2>&1; echo "pytest rc=$?"; tail -25 $OUT/pytest.log
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
 python - <<'PY'
 import json
 try:

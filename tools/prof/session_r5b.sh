@@ -2,7 +2,7 @@
 # the BGZF route with the device's DEFLATE), the sfm step through the C-ABI split phase with one rank and with two ranks on the one GPU
 OUT=gpurun_out/r5b; mkdir -p $OUT
 timeout 600 python -m pytest tests/test_gpu_round5.py tests/test_gpu_round4.py tests/test_gpu_sfm.py tests/test_clean_sam_kat.py tests/test_gpu_round3.py -m gpu -q -p no:cacheprovider > $OUT/pytest.log 2>&1; echo "pytest rc=$?"; tail -30 $OUT/pytest.log
-timeout 500 python bench.py --reads 8000000 --c4-reads 0 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
+timeout 500 python bench.py --full --reads 8000000 --c4-reads 0 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
 timeout 300 python bench.py --mode sfm --reads 8000000 --no-extra --no-cpu-baseline --steps 4 > $OUT/bench_sfm1.json 2> $OUT/bench_sfm1.err; echo "sfm1 rc=$?"; tail -3 $OUT/bench_sfm1.err
 ELP_BENCH_BACKEND=gloo timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --reads 4000000 --steps 3 --warmup 1 > $OUT/bench_sfm2.json 2> $OUT/bench_sfm2.err; echo "sfm2 rc=$?"; tail -5 $OUT/bench_sfm2.err
 python - <<'PY'

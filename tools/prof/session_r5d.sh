@@ -1,7 +1,7 @@
 # round-5 session d: tests of the rows form, the merge across ranks, many read groups (apply record kernels changed); bench extras
 OUT=gpurun_out/r5d; mkdir -p $OUT
 timeout 500 python -m pytest tests/test_gpu_round5.py tests/test_gpu_round3.py tests/test_gpu_harness.py -m gpu -q -p no:cacheprovider > $OUT/pytest.log 2>&1; echo "pytest rc=$?"; tail -12 $OUT/pytest.log
-timeout 500 python bench.py --reads 8000000 --c4-reads 0 --cpu-reads 2000000 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
+timeout 500 python bench.py --full --reads 8000000 --c4-reads 0 --cpu-reads 2000000 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
 python - <<'PY'
 import json
 try:

@@ -2,7 +2,7 @@
 # Round 5: where the host's table path spends its time in the side runs (3 steps after 1 warm-up report 2 ms for tables the main line
 # finalises in 0.45 ms): per-step parts with 8 steps after 2 warm-ups.
 TAG=${1:-r5j}; OUT=gpurun_out/$TAG; mkdir -p $OUT
-ELP_BENCH_HOST_PARTS=1 ELP_BENCH_SIDE_STEPS=8 ELP_BENCH_SIDE_WARMUP=2 timeout 600 python bench.py --reads 16000000 --steps 6 --warmup 2 --no-cpu-baseline --c4-reads 0 > $OUT/bench.json 2> $OUT/bench.err; echo "rc=$?"
+ELP_BENCH_HOST_PARTS=1 ELP_BENCH_SIDE_STEPS=8 ELP_BENCH_SIDE_WARMUP=2 timeout 600 python bench.py --full --reads 16000000 --steps 6 --warmup 2 --no-cpu-baseline --c4-reads 0 > $OUT/bench.json 2> $OUT/bench.err; echo "rc=$?"
 TAG=$TAG python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/'+__import__('os').environ.get('TAG','r5j')+'/bench.json').read().strip().splitlines()[-1])
