@@ -247,7 +247,7 @@ struct elp_ctx {
     long long bgzf_piece = 1ll << 30;    // elp_stage_bgzf: inflated bytes per device pass (tests: small pieces, records pending across them)
     int bgzf_weak_guess = 0;   // 1: a block guesses its first record start without looking at the bytes (tests: every guess wrong, all repaired)
     int score_kernel = 0;      // 1: the general (flat) score kernel even for read sets of one length
-    int mate_path = 0;         // 1: every mate candidate goes through the table path (no neighbour shortcut)
+    int mate_path = 0;         // 2: every mate candidate goes through the table in HBM (no neighbour shortcut)
     int radix_tile = 0;        // 1: radix passes in tiles of 4096 keys whatever the length; 2: of 8192 (default: 8192 from 8 M keys on)
     int sort_pairs = 0;        // 1: the coordinate sort moves (key, index) pairs even where key << b | index fits one word
     int tie_rounds = 0;        // 1: the sort's long runs by LSD rounds over every live position (no key-then-compare shortcut)
@@ -259,7 +259,6 @@ struct elp_ctx {
     int bgzf_first_chunk_div = 4;  // the first H2D chunk is 1/div of the others
     int bgzf_fixed = 0;        // 1: elp_emit_sorted_bgzf writes fixed Huffman codes only (round 5's form) instead of dynamic codes
     int bgzf_tok_fail_above = 0;  // (tests) the token scratch "does not fit" for more than this many blocks: the halving path
-    int bgzf_inflate = 0;      // 1: elp_stage_bgzf inflates with round 5's one-kernel decoder (window in LDS) instead of tokens + resolve
     int bgzf_stored = 0;       // 1: elp_emit_sorted_bgzf writes stored DEFLATE blocks (round 4's form) instead of compressing
     int apply_wgs = 0;         // 1 .. 3: workgroups per CU of the one-length ApplyBQSR kernel (default: as many as its LDS allows, at most 3) - A/B runs
                                // of a step whose sort runs at the same time and needs LDS of its own
@@ -268,8 +267,6 @@ struct elp_ctx {
                                // keep every CU partly occupied)
     int side_priority = 0;     // 1: the side lanes' streams are made with the highest priority the device offers (default: the default priority;
                                // measured with the bench's step: no difference)
-    int md_fused = 0;          // 1: mark duplicates by the separate passes of rounds 2-5 (adapt_fixed, md_keys, md_mate_scan, md_mate_pairs) instead of
-                               // the fused front pass of round 6 (k_md_front); tests run both
   } tune;
 
   // generic scratch pool (grown on demand, reused between calls)

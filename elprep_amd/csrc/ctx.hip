@@ -586,22 +586,24 @@ int elp_set_tuning(elp_ctx *c, const char *key, int64_t value) {
     if (v == 0) { c->tune.pair_table_slots = 1 << 20; return 0; }
     if (v < 2 || v > (1 << 20) || (v & (v - 1))) return set_error(c, ELP_ERR_ARG, "elp_set_tuning: pair_table_slots must be a power of two >= 2");
     c->tune.pair_table_slots = v;
-  } else if (k == "mate_path") c->tune.mate_path = v;
-  else if (k == "tie_rounds") c->tune.tie_rounds = v;
+  } else if (k == "mate_path") {
+    if (value != 0 && value != 2) return set_error(c, ELP_ERR_ARG, "elp_set_tuning: mate_path is 0 (the library decides) or 2 (every candidate through the table)");
+    c->tune.mate_path = v;
+  } else if (k == "tie_rounds") c->tune.tie_rounds = v;
   else if (k == "radix_tile") c->tune.radix_tile = v;
   else if (k == "sort_pairs") c->tune.sort_pairs = v;
   else if (k == "exchange_piece") c->tune.exchange_piece = v;
   else if (k == "emit_pass") c->tune.emit_pass = v;
   else if (k == "bgzf_stored") c->tune.bgzf_stored = v;
-  else if (k == "bgzf_inflate") c->tune.bgzf_inflate = v;
   else if (k == "bgzf_tok_fail_above") c->tune.bgzf_tok_fail_above = v;
   else if (k == "bgzf_fixed") c->tune.bgzf_fixed = v;
   else if (k == "bgzf_first_chunk_div") c->tune.bgzf_first_chunk_div = v;
   else if (k == "bgzf_tok_lds") c->tune.bgzf_tok_lds = v;
   else if (k == "bgzf_copy_chunk") c->tune.bgzf_copy_chunk = v;
   else if (k == "bgzf_inflate_piece") { if (value < 1) return set_error(c, ELP_ERR_ARG, "elp_set_tuning: bgzf_inflate_piece must be positive"); c->tune.bgzf_inflate_piece = value; }
-  else if (k == "md_fused") c->tune.md_fused = v;
-  else if (k == "apply_wgs") c->tune.apply_wgs = v;
+  else if (k == "md_fused" || k == "bgzf_inflate") {  // retired: 0 (what every context does) is still accepted
+    if (value != 0) return set_error(c, ELP_ERR_ARG, "elp_set_tuning: key '%s' is retired (only 0 is accepted)", key);
+  } else if (k == "apply_wgs") c->tune.apply_wgs = v;
   else if (k == "presort_tile") c->tune.presort_tile = v;
   else if (k == "side_priority") c->tune.side_priority = v;
   else return set_error(c, ELP_ERR_ARG, "elp_set_tuning: unknown key '%s'", key);

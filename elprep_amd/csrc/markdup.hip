@@ -21,7 +21,7 @@
 namespace elp {
 
 constexpr uint32_t EMPTY = 0xFFFFFFFFu;
-constexpr unsigned long long PB_EMPTY = ~0ull;  // an empty slot of the LDS tables (k_pair_bucket, k_mate_bucket)
+constexpr unsigned long long PB_EMPTY = ~0ull;  // an empty slot of k_pair_bucket's LDS table
 
 struct MdCols {
   uint64_t n;
@@ -50,47 +50,9 @@ __device__ __forceinline__ unsigned long long ld_agent64(const unsigned long lon
 // The fragment key of a record in one 16-byte word: {REFID, unclipped 5' position, LIBID << 1 | reversed, split id}.  A probe that lands on
 // an occupied slot compares against ONE random 16-byte load instead of four column gathers (the tables are at the random-access
 // limit of the memory system, so accesses are what counts).
-// the FLAG column the tournaments read: the flags as staged, with records the fused predicates rejected (state 2, filter.hip) made
-// non-candidates - in the reference they never reach the MarkDuplicates filter (cmd/filter.go:696-773)
-__global__ __launch_bounds__(256) void k_md_flag_in(uint64_t n, const uint16_t *__restrict__ flag, const uint8_t *__restrict__ state,
-                                                    uint16_t *__restrict__ flag_in) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) flag_in[i] = state[i] == 2 ? (uint16_t)(flag[i] | F_SECONDARY) : flag[i];
-}
-
-// Also lists the TRUE FRAGMENTS (candidates that are not true pairs: unpaired reads and reads whose mate is unmapped).  They are the
+// Only the TRUE FRAGMENTS (candidates that are not true pairs: unpaired reads and reads whose mate is unmapped) are grouped: they are the
 // only records the fragment map can flag (classifyFragment, :210-251: a true pair is never flagged there, it only turns every true
-// fragment at its key into a duplicate), so only they need grouping; the true pairs look their key up afterwards.  A workgroup
-// handles MK_TILES * 256 records and appends its fragments with one global atomic.
-constexpr int MK_TILES = 16;
-__global__ __launch_bounds__(256) void k_md_keys(MdCols m, uint4 *__restrict__ fkey, uint32_t *__restrict__ flist, uint32_t *nf) {
-  __shared__ uint32_t lq[MK_TILES * 256];
-  __shared__ uint32_t lcount, gbase;
-  if (threadIdx.x == 0) lcount = 0;
-  __syncthreads();
-#pragma unroll 2
-  for (int tile = 0; tile < MK_TILES; tile++) {
-    const uint64_t i = ((uint64_t)blockIdx.x * MK_TILES + (uint64_t)tile) * 256 + threadIdx.x;
-    bool frag = false;
-    if (i < m.n) {
-      const uint16_t f = m.flag_in[i];
-      fkey[i] = make_uint4((uint32_t)m.refid[i], (uint32_t)m.upos[i], ((uint32_t)lib_of(m, (uint32_t)i) << 1) | ((f & F_REVERSED) ? 1u : 0u), (uint32_t)m.split[i]);
-      frag = is_candidate(f) && !is_true_pair(f);
-    }
-    const unsigned long long mask = __ballot(frag);
-    if (mask) {
-      const int lane = threadIdx.x & 63, leader = __ffsll((long long)mask) - 1;
-      uint32_t at = 0;
-      if (lane == leader) at = atomicAdd(&lcount, (uint32_t)__popcll(mask));
-      at = __shfl(at, leader, 64);
-      if (frag) lq[at + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t)i;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) gbase = lcount ? atomicAdd(nf, lcount) : 0u;
-  __syncthreads();
-  for (uint32_t k = threadIdx.x; k < lcount; k += 256) flist[gbase + k] = lq[k];
-}
+// fragment at its key into a duplicate); the true pairs look their key up afterwards (k_md_front).
 __device__ __forceinline__ bool key_eq(const uint4 &a, const uint4 &b) { return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w; }
 __device__ __forceinline__ uint64_t frag_hash(const uint4 &k) {
   const uint64_t h = ((uint64_t)k.x << 32) | k.y;
@@ -123,14 +85,6 @@ __global__ __launch_bounds__(256) void k_frag_insert(MdCols m, const uint4 *__re
   const uint32_t rep = find_or_insert(table, mask, frag_hash(mine), i, [&](uint32_t a, uint32_t) { return key_eq(fkey[a], mine); });
   frep[i] = rep;
   atomicMax(&fbest[rep], (unsigned long long)(uint32_t)m.score[i]);
-}
-__global__ __launch_bounds__(256) void k_frag_init(const uint32_t *__restrict__ flist, uint32_t nf, unsigned long long *__restrict__ fbest,
-                                                   uint32_t *__restrict__ fwinner) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= nf) return;
-  const uint32_t i = flist[j];  // any fragment can become its group's representative
-  fbest[i] = 0;
-  fwinner[i] = EMPTY;
 }
 // every true pair looks its own key up (plain loads: the table is final and small - sized by the fragments, not by the records):
 // a group of fragments at the key of a pair loses as a whole
@@ -230,97 +184,15 @@ __device__ __forceinline__ bool is_mate_candidate(uint16_t f) { return is_candid
 // Mate matching reproduces DeleteOrStore toggling in staging order (:336-340).  Three paths:
 //  (1) neighbours: a run of exactly two neighbouring candidates with the same {split, library, QNAME} (the order an aligner writes
 //      mates in) is a pair WITHOUT touching the hash table - provided no other record shares the key.  Records that are not part of
-//      such a run announce their key in a Bloom filter first (k_mate_scan); a neighbour pair whose key hits the filter takes path (2).
+//      such a run announce their key in a Bloom filter first (k_md_front); a neighbour pair whose key hits the filter takes path (2).
 //  (2) table: the first record of a key to arrive at its slot becomes the slot's representative, the second claims it with one CAS on
 //      mate[representative]; both are the only records of the key, so they are a pair whatever their order.
 //  (3) a third record of a key fails that CAS and marks the key's group BIG; the host then lists the members of the big groups,
 //      sorts them by (representative, staging index) and pairs them up 0-1, 2-3, ... within every group (k_big_collect, k_big_pair).
-// k_mate_scan: code[i] = 0 not a mate candidate, 1 table path, 2 leader / 3 follower of a neighbour pair; hash32 of the leader = the
+// k_md_front: code[i] = 0 not a mate candidate, 1 table path, 2 leader / 3 follower of a neighbour pair; hash32 of the leader = the
 // high half of its key hash (the bits the table index does not use).
 enum : uint8_t { MC_NONE = 0, MC_TABLE = 1, MC_LEAD = 2, MC_FOLLOW = 3, MC_KIND = 3, MC_TABBED = 4 /* k_mate_pairs: went through the mate table */ };
 constexpr uint32_t MATE_BIG = 0xFFFFFFFEu;
-
-// The kernel is bound by memory latency (a wave waits for ~40 dependent loads otherwise), so every load of a record and its
-// neighbour is issued up front in two rounds - fixed columns and QNAME offsets, then library ids and the first 32 bytes of both
-// names - and the tests follow without further loads (names longer than 32 bytes finish in a loop).  Threads 256..258 of the
-// 320-thread workgroup make the three neighbour tests across the block's borders the same way.
-constexpr int MS_THREADS = 320;
-__global__ __launch_bounds__(MS_THREADS) void k_mate_scan(MdCols m, uint8_t *__restrict__ code, uint32_t *__restrict__ hash32, uint32_t *__restrict__ hash_lo, uint32_t *bloom,
-                                                          uint32_t bloom_mask, uint32_t *n_table /* records that announce their key (sizes the table) */) {
-  const uint64_t base = (uint64_t)blockIdx.x * 256;
-  const uint32_t t = threadIdx.x;
-  // a = the record this thread tests against its right neighbour; s_join[a - (base - 2)]
-  const int64_t a_s = t < 256 ? (int64_t)(base + t) : (t == 256 ? (int64_t)base - 2 : (t == 257 ? (int64_t)base - 1 : (t == 258 ? (int64_t)base + 256 : -1)));
-  const bool valid = a_s >= 0 && (uint64_t)a_s + 1 < m.n;          // both a and a + 1 exist
-  const bool own = a_s >= 0 && (uint64_t)a_s < m.n;                 // a exists
-  const uint64_t a = own ? (uint64_t)a_s : 0, b = valid ? a + 1 : a;
-  // round 1
-  const uint16_t fa = m.flag_in[a], fb = m.flag_in[b], ra = m.rgid[a], rb = m.rgid[b], sa = m.split[a], sb = m.split[b];
-  const uint64_t oa = m.qname_off[a], ob = m.qname_off[b], oe = m.qname_off[b + 1];
-  const uint32_t la = (uint32_t)((valid ? ob : oe) - oa), lb = (uint32_t)(oe - ob);
-  // round 2
-  const uint16_t lia = ra == ELP_NIL16 ? (uint16_t)ELP_NIL16 : m.rg_lib[ra], lib_b = rb == ELP_NIL16 ? (uint16_t)ELP_NIL16 : m.rg_lib[rb];
-  const uint8_t *pa = m.qname + oa, *pb = m.qname + ob;
-  const uint64_t a0 = load8(pa), a1 = load8(pa + 8), a2 = load8(pa + 16), a3 = load8(pa + 24);
-  // the neighbour's name is what the next lane loaded as its own: only the last lane of a wave (and the border threads) load it
-  // themselves - the names are the bulk of this kernel's traffic, and every one used to be fetched twice
-  uint64_t b0 = __shfl_down(a0, 1, 64), b1 = __shfl_down(a1, 1, 64), b2 = __shfl_down(a2, 1, 64), b3 = __shfl_down(a3, 1, 64);
-  if ((t & 63u) == 63u || t >= 256u) { b0 = load8(pb); b1 = load8(pb + 8); b2 = load8(pb + 16); b3 = load8(pb + 24); }
-  // first 32 bytes of a's name, zero behind its end (the hash takes them as they are)
-  const uint64_t w0 = la > 0 ? low_bytes(a0, la) : 0ull, w1 = la > 8 ? low_bytes(a1, la - 8) : 0ull, w2 = la > 16 ? low_bytes(a2, la - 16) : 0ull,
-                 w3 = la > 24 ? low_bytes(a3, la - 24) : 0ull;
-  bool join = valid && is_mate_candidate(fa) && is_mate_candidate(fb) && lia == lib_b && sa == sb && la == lb;
-  if (join) {
-    uint64_t diff = w0 ^ (lb > 0 ? low_bytes(b0, lb) : 0ull);
-    diff |= w1 ^ (lb > 8 ? low_bytes(b1, lb - 8) : 0ull);
-    diff |= w2 ^ (lb > 16 ? low_bytes(b2, lb - 16) : 0ull);
-    diff |= w3 ^ (lb > 24 ? low_bytes(b3, lb - 24) : 0ull);
-    join = diff == 0;
-    for (uint32_t k = 32; join && k < la; k += 8) join = low_bytes(load8(pa + k), la - k) == low_bytes(load8(pb + k), la - k);
-  }
-  // s_join[u] = joins(base - 2 + u) for u in [0, 259): every neighbour test of the block is made once
-  __shared__ uint8_t s_join[264];
-  __shared__ uint32_t s_ntab;
-  if (t == 0) s_ntab = 0;
-  if (a_s >= 0 || t >= 256) {
-    const int64_t u = a_s - ((int64_t)base - 2);
-    if (t < 259) s_join[t < 256 ? t + 2 : (t == 256 ? 0 : (t == 257 ? 1 : 258))] = join;
-    (void)u;
-  }
-  __syncthreads();
-  uint8_t cd = MC_NONE;
-  const uint64_t i = base + t;
-  if (t < 256 && i < m.n && is_mate_candidate(fa)) {
-    const uint8_t *j = s_join + t + 2;  // j[0] = joins(i)
-    const bool nx = j[0], pv = j[-1];
-    cd = MC_TABLE;
-    if (nx && !pv && !j[1]) cd = MC_LEAD;
-    else if (pv && !nx && !j[-2]) cd = MC_FOLLOW;
-    if (cd != MC_FOLLOW) {
-      // qname_hash(m, i) from the words at hand
-      uint64_t h = 0x9e3779b97f4a7c15ull ^ la;
-      const uint64_t K = 0xff51afd7ed558ccdull;
-      if (la > 0) h = (h ^ w0) * K + (h >> 29);
-      if (la > 8) h = (h ^ w1) * K + (h >> 29);
-      if (la > 16) h = (h ^ w2) * K + (h >> 29);
-      if (la > 24) h = (h ^ w3) * K + (h >> 29);
-      for (uint32_t k = 32; k < la; k += 8) h = (h ^ low_bytes(load8(pa + k), la - k)) * K + (h >> 29);
-      h = mix64(h ^ ((uint64_t)lia << 48) ^ ((uint64_t)sa << 24));
-      const uint32_t hi = (uint32_t)(h >> 32);
-      hash32[i] = hi;  // (a follower's key is its leader's: hash32[i - 1])
-      if (cd == MC_TABLE) hash_lo[i] = (uint32_t)h;  // (the table's index bits: a neighbour pair that goes there after all computes them again)
-      if (cd != MC_LEAD) atomicOr(&bloom[(hi >> 5) & bloom_mask], 1u << (hi & 31u));
-    }
-  }
-  if (t < 256 && i < m.n) code[i] = cd;
-  // one global atomic per workgroup at most (and none in aligner order, where nearly every record is part of a neighbour pair)
-  const unsigned long long tb = __ballot(cd == MC_TABLE);
-  if ((t & 63) == 0 && tb) atomicAdd(&s_ntab, (uint32_t)__popcll(tb));
-  __syncthreads();
-  // (64 counters, a cache line each: with a few per cent of the records on the table path - the sr-tagged copies of an sfm context, whose
-  // mates sit in another split - every workgroup adds here, and ~200 K adds to ONE word serialise at ~12 ns each: 2 ms, measured)
-  if (t == 0 && s_ntab) atomicAdd(&n_table[(blockIdx.x & 63u) * 16u], s_ntab);
-}
 
 // one bit per 64-byte line of the Bloom filter: set if any announcement landed in the line
 __global__ __launch_bounds__(256) void k_bloom_coarse(const uint32_t *__restrict__ bloom, uint32_t n_lines, uint32_t *__restrict__ coarse) {
@@ -340,7 +212,7 @@ __global__ __launch_bounds__(256) void k_bloom_coarse(const uint32_t *__restrict
 
 // path (2) / (3) of the mate matching for record i: the first record of a key at its table slot becomes the representative, the second
 // claims it with one CAS on mate[representative], a third marks the group BIG
-// h = the record's key hash as k_md_front / k_mate_scan stored it (round 6: it was computed again here - the record's name, its offsets,
+// h = the record's key hash as k_md_front stored it (round 6: it was computed again here - the record's name, its offsets,
 // read group and split, five random sectors per record of input whose mates are not neighbours)
 __device__ __forceinline__ void mate_table_insert(const MdCols &m, const uint4 *__restrict__ fkey, uint32_t i, uint64_t h, uint32_t *table, uint64_t mask, uint32_t *mate,
                                                   uint32_t *rep_of, uint32_t *err) {
@@ -387,11 +259,8 @@ __global__ __launch_bounds__(256) void k_mate_table(MdCols m, const uint4 *__res
   }
 }
 
-// k_mate_pairs - ONE pass over the records behind k_mate_scan does what three passes did (md_mate_insert, md_frag_probe,
-// md_pair_list):
-//  * every true pair looks its own fragment key up in the (final, small) table of the true fragments - plain loads behind the
-//    L2-resident occupancy bits - and sets the pair bit of the group it finds (classifyFragment :210-251: a fragment group that
-//    holds a read of a true pair loses as a whole);
+// k_mate_pairs - the mate pass behind k_md_front where its optimistic pairing does not stand (a record announced its key, or the host
+// saw that most candidates take the table path):
 //  * mates: a neighbour pair nobody else announced is a pair at once; the other mate candidates go through the table (paths 2 and 3
 //    above) and are marked in the code column (MC_TABBED);
 //  * the follower of a neighbour pair is the pair's owner (the later arrival, :336-340) and has both keys and both scores at hand: it
@@ -404,26 +273,19 @@ __global__ __launch_bounds__(256) void k_mate_table(MdCols m, const uint4 *__res
 // bucket kernel skips - no list counter, no staging, a record per thread.  Holes are ~5 % of the slots in aligner order.  Without
 // `fixed` (the host saw that most candidates take the table path) the followers are marked like table pairs and entered afterwards.
 // A thread handles MP_R records (one per 256-record tile of its workgroup) and issues the loads of all of them level by level - codes,
-// keys and name hashes; then occupancy bits, Bloom words, the neighbour's key and the scores; then the fragment table's entry; then
-// that fragment's key: a wave otherwise waits four dependent round trips per record, one after the other, for the sake of the one
-// lane in sixteen whose look-up reaches the table (the one-record-per-thread form ran at the latency of that chain, not at bandwidth).
+// keys and name hashes; then Bloom words, the neighbour's key and the scores - before any test that needs them.
 constexpr int MP_R = 1;
 __global__ __launch_bounds__(256) void k_mate_pairs(MdCols m, const uint4 *__restrict__ fkey, uint8_t *__restrict__ code,
                                                     const uint32_t *__restrict__ hash32, const uint32_t *__restrict__ hash_lo, const uint32_t *__restrict__ bloom,
                                                     uint32_t bloom_mask, const uint32_t *__restrict__ coarse /* null: nobody announced a key */,
-                                                    uint32_t *table, uint64_t mask, uint32_t *mate, uint32_t *rep_of, uint32_t *err,
-                                                    const uint32_t *__restrict__ ftable, const uint32_t *__restrict__ fbits, uint64_t fmask /* 0: no fragments */,
-                                                    unsigned long long *fbest, int fixed /* 2: every candidate is matched by the partitioned pass
-                                                    (k_mate_bucket) - only the fragment look-ups and the marks are made here */,
+                                                    uint32_t *table, uint64_t mask, uint32_t *mate, uint32_t *rep_of, uint32_t *err, int fixed,
                                                     uint64_t *__restrict__ pk, uint32_t *__restrict__ pv,
                                                     uint32_t *__restrict__ tab_list /* null: table inserts are made here */, uint32_t *tab_cnt, uint32_t tab_cap) {
   const uint64_t base = (uint64_t)blockIdx.x * (256 * MP_R) + threadIdx.x;
   uint8_t cd[MP_R];
-  uint4 mine[MP_R], prev[MP_R], kc[MP_R];
-  uint32_t hi[MP_R], hl[MP_R], bl[MP_R], fw[MP_R], cur[MP_R];
+  uint4 mine[MP_R], prev[MP_R];
+  uint32_t hi[MP_R], hl[MP_R], bl[MP_R];
   int32_t sc[MP_R];
-  uint64_t fs[MP_R];
-  bool hit[MP_R];
   // level 0
 #pragma unroll
   for (int r = 0; r < MP_R; r++) {
@@ -440,8 +302,6 @@ __global__ __launch_bounds__(256) void k_mate_pairs(MdCols m, const uint4 *__res
   for (int r = 0; r < MP_R; r++) {
     const uint64_t i = base + (uint64_t)r * 256;
     const bool cand = cd[r] != MC_NONE;
-    fs[r] = frag_hash(mine[r]) & fmask;
-    fw[r] = (cand && fmask) ? fbits[fs[r] >> 5] : 0u;
     // the filter's word, behind a coarse level (one bit per 64-byte line of the filter, 8 KB that stay in the L1): in aligner order
     // next to nobody announces a key, and 48 M look-ups of a 4 MB filter in the L2 cost as much as streaming this kernel's columns
     bl[r] = ~0u;
@@ -453,41 +313,17 @@ __global__ __launch_bounds__(256) void k_mate_pairs(MdCols m, const uint4 *__res
     prev[r] = fol ? fkey[i - 1] : make_uint4(0, 0, 0, 0);
     sc[r] = fol ? m.score[i] + m.score[i - 1] : 0;
   }
-  // level 2, 3: the first probe of the fragment table
-#pragma unroll
-  for (int r = 0; r < MP_R; r++) {
-    hit[r] = (fw[r] >> (fs[r] & 31)) & 1u;
-    cur[r] = hit[r] ? ftable[fs[r]] : 0u;
-  }
-#pragma unroll
-  for (int r = 0; r < MP_R; r++) kc[r] = hit[r] ? fkey[cur[r]] : make_uint4(0, 0, 0, 0);
 #pragma unroll
   for (int r = 0; r < MP_R; r++) {
     const uint64_t i = base + (uint64_t)r * 256;
-    if (hit[r]) {
-      if (key_eq(kc[r], mine[r])) atomicMax(&fbest[cur[r]], 1ull << 63);
-      else {
-        // an occupied slot of another key: on along the probe sequence (rare: the table is sparse)
-        for (uint64_t s = (fs[r] + 1) & fmask;; s = (s + 1) & fmask) {
-          if (!((fbits[s >> 5] >> (s & 31)) & 1u)) break;
-          const uint32_t c2 = ftable[s];
-          if (key_eq(fkey[c2], mine[r])) {
-            atomicMax(&fbest[c2], 1ull << 63);
-            break;
-          }
-        }
-      }
-    }
     bool own = false, want_tab = false;
     uint64_t key = 0;
-    if (cd[r] != MC_NONE && fixed == 2) {
-      code[i] = (uint8_t)(cd[r] | MC_TABBED);
-    } else if (cd[r] != MC_NONE) {  // a candidate that is a true pair
+    if (cd[r] != MC_NONE) {  // a candidate that is a true pair
       const bool tab = cd[r] == MC_TABLE || ((bl[r] >> (hi[r] & 31u)) & 1u);
       if (!tab) {  // nobody else announced this key: the two neighbours are the pair
         mate[i] = cd[r] == MC_LEAD ? (uint32_t)i + 1 : (uint32_t)i - 1;
         if (cd[r] == MC_FOLLOW) {
-          if (fixed == 1) {
+          if (fixed) {
             own = true;
             key = ((uint64_t)(uint32_t)sc[r] << 32) | (uint32_t)pair_hash(pair_key(mine[r], prev[r]));
           } else {
@@ -500,7 +336,7 @@ __global__ __launch_bounds__(256) void k_mate_pairs(MdCols m, const uint4 *__res
         else mate_table_insert(m, fkey, (uint32_t)i, cd[r] == MC_TABLE ? ((uint64_t)hash32[i] << 32) | hl[r] : qname_hash(m, (uint32_t)i), table, mask, mate, rep_of, err);
       }
     }
-    // Round 5: in aligner order the few records that need the table (the sr-tagged copies of an sfm context: 2 % of the records, one or two
+    // In aligner order the few records that need the table (the sr-tagged copies of an sfm context: 2 % of the records, one or two
     // lanes of EVERY wave) are listed for a dense pass of their own (k_mate_table) instead of walking the table here: a wave waited for
     // its one lane's name hash and compare-and-swap in HBM - 63 lanes idle - and the kernel took 1.7 instead of 0.8 ms.  64 lists, a wave
     // appends to list (workgroup % 64) with one atomic on that list's counter (a cache line of its own).
@@ -515,7 +351,7 @@ __global__ __launch_bounds__(256) void k_mate_pairs(MdCols m, const uint4 *__res
         if (want_tab) tab_list[(size_t)li * tab_cap + at] = (uint32_t)i;
       }
     }
-    if (fixed == 1) {
+    if (fixed) {
       const int next_owns = __shfl_down((int)own, 1, 64);
       if (own) {
         pk[i >> 1] = key;
@@ -524,81 +360,6 @@ __global__ __launch_bounds__(256) void k_mate_pairs(MdCols m, const uint4 *__res
         pk[i >> 1] = 0xFFFFFFFF00000000ull | (uint32_t)mix64(i);
         pv[i >> 1] = EMPTY;
       }
-    }
-  }
-}
-
-// ---- mates that are NOT neighbours (coordinate-ordered or shuffled input: every candidate would go through the table in HBM, one
-// random compare-and-swap each).  The same remedy as for the pairs: the candidates' {32 hash bits of the mate key, record} entries are
-// partitioned by hash bits (the sort's scatter passes), one workgroup per bucket matches its entries in an LDS table.  The table pairs
-// records up exactly as the global one does (first at the slot = representative, the second claims it, a third marks the group BIG for
-// the arrival-order pairing) - DeleteOrStore toggling, :336-340.
-constexpr int ML_TILES = 8;
-__global__ __launch_bounds__(256) void k_mate_list(uint64_t n, const uint8_t *__restrict__ code, const uint32_t *__restrict__ hash32, uint64_t *__restrict__ mk,
-                                                   uint32_t *__restrict__ mv, uint32_t *ne) {
-  __shared__ uint64_t lk[ML_TILES * 256];
-  __shared__ uint32_t lv[ML_TILES * 256];
-  __shared__ uint32_t lcount, gbase;
-  if (threadIdx.x == 0) lcount = 0;
-  __syncthreads();
-#pragma unroll 2
-  for (int tile = 0; tile < ML_TILES; tile++) {
-    const uint64_t i = ((uint64_t)blockIdx.x * ML_TILES + (uint64_t)tile) * 256 + threadIdx.x;
-    const uint8_t cd = i < n ? (uint8_t)(code[i] & MC_KIND) : (uint8_t)MC_NONE;
-    const bool cand = cd != MC_NONE;
-    const uint32_t h = cand ? hash32[cd == MC_FOLLOW ? i - 1 : i] : 0u;
-    const unsigned long long mask = __ballot(cand);
-    if (mask) {
-      const int lane = threadIdx.x & 63, leader = __ffsll((long long)mask) - 1;
-      uint32_t at = 0;
-      if (lane == leader) at = atomicAdd(&lcount, (uint32_t)__popcll(mask));
-      at = __shfl(at, leader, 64);
-      if (cand) {
-        at += (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-        lk[at] = (uint64_t)h;
-        lv[at] = (uint32_t)i;
-      }
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) gbase = lcount ? atomicAdd(ne, lcount) : 0u;
-  __syncthreads();
-  for (uint32_t k = threadIdx.x; k < lcount; k += 256) {
-    mk[gbase + k] = lk[k];
-    mv[gbase + k] = lv[k];
-  }
-}
-constexpr int MB_TARGET = 640, MB_CAP = 2048;
-__global__ __launch_bounds__(256) void k_mate_bucket(MdCols m, const uint4 *__restrict__ fkey, const uint64_t *__restrict__ ks, const uint32_t *__restrict__ vs,
-                                                     const uint32_t *__restrict__ bstart, const uint32_t *__restrict__ bend, uint32_t *mate, uint32_t *rep_of, uint32_t *err) {
-  __shared__ unsigned long long s_key[MB_CAP];  // hash bits << 32 | representative (the first record of its key to arrive at the slot)
-  __shared__ uint32_t s_mate[MB_CAP];           // the second one
-  const uint32_t start = bstart[blockIdx.x], cnt = bend[blockIdx.x] - start;
-  if (cnt == 0) return;
-  const uint32_t t = threadIdx.x;
-  uint32_t T = 2;
-  while (T < 2 * cnt && T < (uint32_t)MB_CAP) T <<= 1;
-  const uint32_t tmask = T - 1;
-  for (uint32_t k = t; k < T; k += 256) { s_key[k] = PB_EMPTY; s_mate[k] = EMPTY; }
-  __syncthreads();
-  for (uint32_t e = t; e < cnt; e += 256) {
-    const uint32_t h32 = (uint32_t)ks[start + e], i = vs[start + e];
-    const unsigned long long mine = ((unsigned long long)h32 << 32) | i;
-    uint32_t idx = ((h32 * 0x9E3779B1u) >> 16) & tmask;
-    uint32_t rep = EMPTY, slot = 0;
-    for (uint32_t probes = 0; probes <= tmask; probes++, idx = (idx + 1) & tmask) {
-      const unsigned long long cur = atomicCAS(&s_key[idx], PB_EMPTY, mine);
-      if (cur == PB_EMPTY) { rep = i; slot = idx; break; }
-      if ((uint32_t)(cur >> 32) == h32 && mate_key_eq(m, fkey, (uint32_t)cur, fkey[i], i)) { rep = (uint32_t)cur; slot = idx; break; }
-    }
-    if (rep == EMPTY) { atomicOr(&err[1], 4u); continue; }  // the table is full (keys crafted to share hash bits): the host takes the table in HBM
-    if (rep == i) continue;  // first of its key at the slot: waits for the second
-    rep_of[i] = rep;
-    const uint32_t old = atomicCAS(&s_mate[slot], EMPTY, i);
-    if (old == EMPTY) { mate[i] = rep; mate[rep] = i; }
-    else {
-      rep_of[rep] = MATE_BIG;  // more than two records share {split, library, QNAME}
-      atomicOr(&err[1], 1u);
     }
   }
 }
@@ -902,19 +663,18 @@ __global__ __launch_bounds__(PB_THREADS) void k_pair_bucket(MdCols m, const uint
   }
 }
 
-// ---------------- the front pass (round 6; VERDICT r5 next #1a / #1b)
-// Rounds 2-5 streamed the fixed fields four times before the pair phase: k_adapt_fixed (unclipped positions, sort keys), k_md_keys (packed
-// fragment keys, list of true fragments), k_mate_scan (neighbour test on the names) and k_mate_pairs (fragment look-ups, neighbour pairs,
-// pair entries) - 180 bytes per read where the data is ~100.  k_md_front makes ONE pass of them:
+// ---------------- the front pass
+// The fixed fields are streamed ONCE before the pair phase (unclipped positions, sort keys, packed fragment keys, the neighbour test on the
+// names, the fragment look-ups, neighbour pairs and pair entries: ~100 bytes per read):
 //   k_frag_list   the true fragments (~0.5 % of paired-end reads) are listed from the FLAG column alone, their keys (unclipped position
 //                 from the CIGAR) and group payloads written; the host reads the list's length while the score kernel runs;
 //   (k_frag_insert, k_frag_bits: the fragments' table is FINAL before any pair looks its key up)
-//   k_md_front    a record per thread (+ three border threads per 256 records, as k_mate_scan): every load of the record is issued up front;
+//   k_md_front    a record per thread: every load of the record is issued up front;
 //                 unclipped position, sort key (when the adapt stage has not run yet), packed key, the neighbour test, code / name hash /
 //                 Bloom announcement of the records that are not exactly-two-neighbours, the fragment look-up of every true pair, and -
 //                 optimistically - the neighbour pairs' mates and entries at their fixed slots, as if nobody announced a key.  In
 //                 aligner order nobody does (the count comes back with the call's one read-back) and the mate phase is over; otherwise the
-//                 mates are cleared and k_mate_pairs redoes them with the filter, the table and the lists, as before.
+//                 mates are cleared and k_mate_pairs redoes them with the filter, the table and the lists.
 // the value the NEXT lane of the wave holds (lane 63: unspecified): one DPP move - a ds_bpermute takes six times the issue time
 // (profiles/r3m_isa_rate_probe.txt).  Every lane of the wave must be active.
 __device__ __forceinline__ uint32_t next_lane(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x130 /* wave_shl:1 */, 0xf, 0xf, false); }
@@ -924,7 +684,7 @@ struct FrontCols {
   uint64_t n;
   const int32_t *refid, *pos;
   const uint16_t *flag;   // as staged
-  const uint8_t *state;   // the has_sr column: 0 live, 1 sr-tagged copy, 2 rejected by the fused predicates (never a candidate: k_md_flag_in)
+  const uint8_t *state;   // the has_sr column: 0 live, 1 sr-tagged copy, 2 rejected by the fused predicates (never a candidate: flag_in_of)
   const uint16_t *rgid, *rg_lib, *split;
   const uint64_t *cigar_off;
   const uint32_t *cigar;
@@ -962,6 +722,8 @@ __device__ __forceinline__ int32_t unclipped_pos(uint16_t f, int32_t p, uint64_t
   }
   return up;
 }
+// the FLAG the tournaments read: the flag as staged, with records the fused predicates rejected (state 2, filter.hip) made non-candidates -
+// in the reference they never reach the MarkDuplicates filter (cmd/filter.go:696-773)
 __device__ __forceinline__ uint16_t flag_in_of(uint16_t f, uint8_t state) { return state == 2 ? (uint16_t)(f | F_SECONDARY) : f; }
 
 // (a thread takes eight consecutive records per round: one 16-byte load of their flags, one 8-byte load of their states.  A few persistent
@@ -1110,7 +872,7 @@ __global__ __launch_bounds__(MF_THREADS) void k_md_front(FrontCols m, const int3
       h = mix64(h ^ ((uint64_t)lia << 48) ^ ((uint64_t)sa << 24));
       const uint32_t hi = (uint32_t)(h >> 32);
       hash32[i] = hi;
-      if (cd == MC_TABLE) hash_lo[i] = (uint32_t)h;  // (as k_mate_scan)
+      if (cd == MC_TABLE) hash_lo[i] = (uint32_t)h;  // (the table's index bits: a neighbour pair that goes there after all computes them again)
       if (cd != MC_LEAD) atomicOr(&bloom[(hi >> 5) & bloom_mask], 1u << (hi & 31u));
     }
   }
@@ -1154,26 +916,15 @@ static int markdup_impl(elp_ctx *c) {
   ELP_TRY(ensure(c, c->mate, n + 1));
   ELP_TRY(ensure(c, c->pair_win, n + 1));
   if (n == 0) { ELP_TRY(ensure_adapted(c, true)); c->marked = true; return 0; }
-  const bool fused = c->tune.md_fused != 1;
   // the front pass also does the adapt stage's fixed-field part when that has not run yet (what a host that marks duplicates first - the
   // reference's order, cmd/filter.go:142-211 - gets)
-  const bool fuse_adapt = fused && !c->adapted;
+  const bool fuse_adapt = !c->adapted;
   int pos_bits = 1;
   if (fuse_adapt) ELP_TRY(adapt_begin(c, &pos_bits));
   else ELP_TRY(ensure_adapted(c, false));  // (its quality-error word is read with this call's first read-back, below)
   const unsigned grid = blocks_for(n, 256);
   hipStream_t st = c->stream;
-  // flag_in: tournaments see the flags as staged, with the records the fused predicates rejected made non-candidates.  The front pass
-  // derives it from the state column as it goes; the separate passes read a patched copy
-  uint16_t *flag_in = c->flag.p;
-  if (!fused) {
-    ELP_TRY(scratch(c, 4, n + 8, &flag_in));
-    if (c->n_filtered)
-      ELP_LAUNCH(c, "md_flag_in", k_md_flag_in, dim3(grid), dim3(256), 0, n, (const uint16_t *)c->flag.p, (const uint8_t *)c->has_sr.p, flag_in);
-    else
-      ELP_HIP(c, hipMemcpyAsync(flag_in, c->flag.p, n * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
-  }
-  MdCols m{n, c->refid.p, flag_in, c->rgid.p, c->rg_lib.p, c->split.p, c->upos.p, c->score.p, c->qname_off.p, c->qname.p};
+  MdCols m{n, c->refid.p, c->flag.p, c->rgid.p, c->rg_lib.p, c->split.p, c->upos.p, c->score.p, c->qname_off.p, c->qname.p};
   const uint64_t T = table_size_for(n);
   uint32_t *table;
   ELP_TRY(scratch(c, 0, T, &table));
@@ -1191,19 +942,14 @@ static int markdup_impl(elp_ctx *c) {
   ELP_TRY(scratch(c, 1, 2 * n + 16, &rep));
   uint32_t *flist = rep + n + 8;
   ELP_HIP(c, hipMemsetAsync(c->md_ctr.p, 0, (16 + 64 * 16) * sizeof(uint32_t), st));  // every counter of this call in one fill
-  uint32_t nf = 0;
   FrontCols fc{n, c->refid.p, c->pos.p, c->flag.p, c->has_sr.p, c->rgid.p, c->rg_lib.p, c->split.p, c->cigar_off.p, c->cigar.p, c->qname_off.p, c->qname.p,
                (uint32_t)c->n_ref, pos_bits};
-  if (fused) {
-    // the list's length comes back through the mailbox while the stream runs on (the score kernel, when the adapt stage is this call's)
-    ELP_TRY(mailbox(c));
-    ELP_LAUNCH(c, "md_frag_list", k_frag_list, dim3(std::min<unsigned>(blocks_for(n, FLI_CHUNK), (unsigned)c->n_cu * 8)), dim3(256), 0, fc, fkey, flist, nf_dev, best, winner);
-    ELP_HIP(c, hipMemcpyAsync(c->mail, nf_dev, 4, hipMemcpyDeviceToHost, st));
-    ELP_HIP(c, hipEventRecord(c->mail_ev, st));
-    if (fuse_adapt) ELP_TRY(adapt_scores(c));
-  } else {
-    ELP_LAUNCH(c, "md_keys", k_md_keys, dim3(blocks_for(n, 256 * MK_TILES)), dim3(256), 0, m, fkey, flist, nf_dev);  // (nf: read with the mate phase's table estimate below)
-  }
+  // the list's length comes back through the mailbox while the stream runs on (the score kernel, when the adapt stage is this call's)
+  ELP_TRY(mailbox(c));
+  ELP_LAUNCH(c, "md_frag_list", k_frag_list, dim3(std::min<unsigned>(blocks_for(n, FLI_CHUNK), (unsigned)c->n_cu * 8)), dim3(256), 0, fc, fkey, flist, nf_dev, best, winner);
+  ELP_HIP(c, hipMemcpyAsync(c->mail, nf_dev, 4, hipMemcpyDeviceToHost, st));
+  ELP_HIP(c, hipEventRecord(c->mail_ev, st));
+  if (fuse_adapt) ELP_TRY(adapt_scores(c));
 
   // the pair phase's list, partitioned by hash bits: at most n / 2 pairs
   int bbits = 0;
@@ -1229,51 +975,39 @@ static int markdup_impl(elp_ctx *c) {
   ELP_HIP(c, hipMemsetAsync(bloom, 0, bw * sizeof(uint32_t), st));
   uint32_t n_tab = 0, n_tab64[64 * 16];
   uint32_t adapt_word[ADAPT_WORDS] = {0, 0, 0, 0, 0, 0};
-  uint64_t npmax = 0, nfixed = 0, Tf = 0;
-  uint64_t *pk = nullptr;
-  uint32_t *pv = nullptr, *ftable = nullptr, *fbits = nullptr;
-  unsigned fgrid = 0;
-  bool fixed = false, frag_done = false, fast = false;
-  if (fused) {
-    // the fragments' table first: it is final before any pair looks its key up
-    ELP_HIP(c, elp::event_wait(c->mail_ev));
-    nf = c->mail[0];
-    fgrid = blocks_for(nf, 256);
-    Tf = nf ? std::min<uint64_t>(T, table_size_for(4ull * nf)) : 0;  // sparse: most look-ups of the pairs end at an empty slot
-    npmax = n + 2;  // (whatever the mates' order turns out to be)
-    ELP_TRY(scratch(c, 7, 2 * npmax + (2 * npmax + Tf + Tf / 32 + 64) / 2 + 8, &pk));
-    pv = reinterpret_cast<uint32_t *>(pk + 2 * npmax); ftable = pv + 2 * npmax; fbits = ftable + Tf;
-    if (nf) {
-      ELP_HIP(c, hipMemsetAsync(ftable, 0xFF, Tf * sizeof(uint32_t), st));
-      ELP_LAUNCH(c, "md_frag_insert", k_frag_insert, dim3(fgrid), dim3(256), 0, m, (const uint4 *)fkey, (const uint32_t *)flist, nf, ftable, Tf - 1, rep, best);
-      ELP_LAUNCH(c, "md_frag_bits", k_frag_bits, dim3(blocks_for(Tf / 32, 256)), dim3(256), 0, (const uint32_t *)ftable, Tf / 32, fbits);
-    }
-    const int optimistic = c->tune.mate_path == 0;
-    const uint32_t nfx = (uint32_t)((n + 1) / 2);
-    if (fuse_adapt)
-      ELP_LAUNCH(c, "md_front", k_md_front<true>, dim3(blocks_for(n, MF_RECS)), dim3(MF_THREADS), 0, fc, (const int32_t *)c->score.p, c->upos.p, c->key.p, fkey, code, hash32, hash_lo, bloom,
-                 (uint32_t)(bw - 1), n_table_dev, (const uint32_t *)ftable, (const uint32_t *)fbits, nf ? Tf - 1 : (uint64_t)0, best, c->mate.p, c->pair_win.p, pk, pv,
-                 np_dev, nfx, optimistic);
-    else
-      ELP_LAUNCH(c, "md_front", k_md_front<false>, dim3(blocks_for(n, MF_RECS)), dim3(MF_THREADS), 0, fc, (const int32_t *)c->score.p, c->upos.p, c->key.p, fkey, code, hash32, hash_lo, bloom,
-                 (uint32_t)(bw - 1), n_table_dev, (const uint32_t *)ftable, (const uint32_t *)fbits, nf ? Tf - 1 : (uint64_t)0, best, c->mate.p, c->pair_win.p, pk, pv,
-                 np_dev, nfx, optimistic);
-    if (fuse_adapt) c->adapted = true;
-    // elp_sort_ahead: the keys exist - the coordinate sort's key passes go to the sort lane now and run under the pair phase
-    ELP_TRY(sort_presort(c));
-    // tournament among the fragments of pair-free groups (the pair bits are complete): queued in front of the read-back
-    if (nf) {
-      ELP_LAUNCH(c, "md_frag_tie", k_frag_tie, dim3(fgrid), dim3(256), 0, m, (const uint32_t *)flist, nf, (const uint32_t *)rep,
-                 (const unsigned long long *)best, winner);
-      ELP_LAUNCH(c, "md_frag_flag", k_frag_flag, dim3(fgrid), dim3(256), 0, m, (const uint32_t *)flist, nf, (const uint32_t *)rep,
-                 (const unsigned long long *)best, (const uint32_t *)winner, c->flag.p);
-    }
-    frag_done = true;
-  } else {
-    ELP_HIP(c, hipMemsetAsync(c->mate.p, 0xFF, n * sizeof(uint32_t), st));
-    ELP_HIP(c, hipMemsetAsync(rep_of, 0xFF, n * sizeof(uint32_t), st));
-    ELP_LAUNCH(c, "md_mate_scan", k_mate_scan, dim3(grid), dim3(MS_THREADS), 0, m, code, hash32, hash_lo, bloom, (uint32_t)(bw - 1), n_table_dev);
-    ELP_HIP(c, hipMemcpyAsync(&nf, nf_dev, 4, hipMemcpyDeviceToHost, st));
+  // the fragments' table first: it is final before any pair looks its key up
+  ELP_HIP(c, elp::event_wait(c->mail_ev));
+  const uint32_t nf = c->mail[0];
+  const unsigned fgrid = blocks_for(nf, 256);
+  const uint64_t Tf = nf ? std::min<uint64_t>(T, table_size_for(4ull * nf)) : 0;  // sparse: most look-ups of the pairs end at an empty slot
+  const uint64_t npmax = n + 2;  // (whatever the mates' order turns out to be)
+  uint64_t *pk;
+  ELP_TRY(scratch(c, 7, 2 * npmax + (2 * npmax + Tf + Tf / 32 + 64) / 2 + 8, &pk));
+  uint32_t *pv = reinterpret_cast<uint32_t *>(pk + 2 * npmax), *ftable = pv + 2 * npmax, *fbits = ftable + Tf;
+  if (nf) {
+    ELP_HIP(c, hipMemsetAsync(ftable, 0xFF, Tf * sizeof(uint32_t), st));
+    ELP_LAUNCH(c, "md_frag_insert", k_frag_insert, dim3(fgrid), dim3(256), 0, m, (const uint4 *)fkey, (const uint32_t *)flist, nf, ftable, Tf - 1, rep, best);
+    ELP_LAUNCH(c, "md_frag_bits", k_frag_bits, dim3(blocks_for(Tf / 32, 256)), dim3(256), 0, (const uint32_t *)ftable, Tf / 32, fbits);
+  }
+  const int optimistic = c->tune.mate_path == 0;
+  const uint32_t nfx = (uint32_t)((n + 1) / 2);
+  if (fuse_adapt)
+    ELP_LAUNCH(c, "md_front", k_md_front<true>, dim3(blocks_for(n, MF_RECS)), dim3(MF_THREADS), 0, fc, (const int32_t *)c->score.p, c->upos.p, c->key.p, fkey, code, hash32, hash_lo, bloom,
+               (uint32_t)(bw - 1), n_table_dev, (const uint32_t *)ftable, (const uint32_t *)fbits, nf ? Tf - 1 : (uint64_t)0, best, c->mate.p, c->pair_win.p, pk, pv,
+               np_dev, nfx, optimistic);
+  else
+    ELP_LAUNCH(c, "md_front", k_md_front<false>, dim3(blocks_for(n, MF_RECS)), dim3(MF_THREADS), 0, fc, (const int32_t *)c->score.p, c->upos.p, c->key.p, fkey, code, hash32, hash_lo, bloom,
+               (uint32_t)(bw - 1), n_table_dev, (const uint32_t *)ftable, (const uint32_t *)fbits, nf ? Tf - 1 : (uint64_t)0, best, c->mate.p, c->pair_win.p, pk, pv,
+               np_dev, nfx, optimistic);
+  if (fuse_adapt) c->adapted = true;
+  // elp_sort_ahead: the keys exist - the coordinate sort's key passes go to the sort lane now and run under the pair phase
+  ELP_TRY(sort_presort(c));
+  // tournament among the fragments of pair-free groups (the pair bits are complete): queued in front of the read-back
+  if (nf) {
+    ELP_LAUNCH(c, "md_frag_tie", k_frag_tie, dim3(fgrid), dim3(256), 0, m, (const uint32_t *)flist, nf, (const uint32_t *)rep,
+               (const unsigned long long *)best, winner);
+    ELP_LAUNCH(c, "md_frag_flag", k_frag_flag, dim3(fgrid), dim3(256), 0, m, (const uint32_t *)flist, nf, (const uint32_t *)rep,
+               (const unsigned long long *)best, (const uint32_t *)winner, c->flag.p);
   }
   // the table only has to hold the records that are not exactly-two-neighbours (few in aligner order) plus the neighbour pairs a
   // Bloom-filter hit sends there (at most as many again, in practice a fraction): size it by their number, not by n
@@ -1286,100 +1020,36 @@ static int markdup_impl(elp_ctx *c) {
   for (int k = 0; k < 64; k++) n_tab += n_tab64[k * 16];
 
   // aligner order (few candidates need a table): the neighbour pairs' entries go to fixed slots, the table's pairs behind them.  Else
-  // (coordinate-ordered, shuffled input) every candidate is matched by the partitioned pass (k_mate_list, k_mate_bucket)
-  fixed = (uint64_t)n_tab < n / 8 && c->tune.mate_path == 0;
-  // 1 neighbours + table in HBM for the rest, 2 partitioned, 0 table in HBM for all.  Measured (16 M reads staged in random order,
-  // tools/prof/shuffled_md.py): partitioned 1.59 (buckets) + 0.32 (two scatter passes) + 0.15 (list, bounds) ms, table in HBM 1.84 ms - both
-  // are bound by the ~10 random loads of the key comparison every pair needs once (two names, their offsets, read group -> library, split),
-  // not by the insert; the table in HBM therefore stays the default for input whose mates are not neighbours
-  int mate_mode = fixed ? 1 : (c->tune.mate_path == 1 ? 2 : 0);
-  nfixed = fixed ? (n + 1) / 2 : 0;
-  if (!fused) {
-    npmax = std::max<uint64_t>(nfixed + n / 2 + 1, fixed ? 0 : n + 1);
-    // pair list (two buffers each for the radix passes; the partitioned mate pass uses them first) | fragment table and its occupancy bits
-    Tf = nf ? std::min<uint64_t>(T, table_size_for(4ull * nf)) : 0;  // sparse: most look-ups of the pairs end at an empty slot
-    ELP_TRY(scratch(c, 7, 2 * npmax + (2 * npmax + Tf + Tf / 32 + 64) / 2 + 8, &pk));
-    pv = reinterpret_cast<uint32_t *>(pk + 2 * npmax); ftable = pv + 2 * npmax; fbits = ftable + Tf;
-    // fragments: group the true fragments (their table is final before the pairs look their keys up)
-    fgrid = blocks_for(nf, 256);
-    if (nf) {
-      ELP_HIP(c, hipMemsetAsync(ftable, 0xFF, Tf * sizeof(uint32_t), st));
-      ELP_LAUNCH(c, "md_frag_init", k_frag_init, dim3(fgrid), dim3(256), 0, (const uint32_t *)flist, nf, best, winner);
-      ELP_LAUNCH(c, "md_frag_insert", k_frag_insert, dim3(fgrid), dim3(256), 0, m, (const uint4 *)fkey, (const uint32_t *)flist, nf, ftable, Tf - 1, rep, best);
-      ELP_LAUNCH(c, "md_frag_bits", k_frag_bits, dim3(blocks_for(Tf / 32, 256)), dim3(256), 0, (const uint32_t *)ftable, Tf / 32, fbits);
-    }
-  } else {
-    // nobody announced a key: the front pass's neighbour pairs stand (mates, entries at their fixed slots, pair_win all EMPTY)
-    fast = fixed && n_tab == 0;
-    if (!fast) ELP_HIP(c, hipMemsetAsync(c->mate.p, 0xFF, n * sizeof(uint32_t), st));  // (rep_of = pair_win is all EMPTY from the front pass)
-  }
+  // (coordinate-ordered, shuffled input, or mate_path = 2) every candidate goes through the table in HBM.  (A pass that partitions the
+  // candidates by hash bits into LDS tables was measured no faster on shuffled input: both are bound by the ~10 random loads of the key
+  // comparison every pair needs once - two names, their offsets, read group -> library, split -, not by the insert.)
+  const bool fixed = (uint64_t)n_tab < n / 8 && c->tune.mate_path == 0;
+  const uint64_t nfixed = fixed ? (n + 1) / 2 : 0;
+  // nobody announced a key: the front pass's neighbour pairs stand (mates, entries at their fixed slots, pair_win all EMPTY)
+  const bool fast = fixed && n_tab == 0;
+  if (!fast) ELP_HIP(c, hipMemsetAsync(c->mate.p, 0xFF, n * sizeof(uint32_t), st));  // (rep_of = pair_win is all EMPTY from the front pass)
   if (n_tab && !fast) ELP_LAUNCH(c, "md_bloom_coarse", k_bloom_coarse, dim3(blocks_for(bw / 16, 256)), dim3(256), 0, (const uint32_t *)bloom, (uint32_t)(bw / 16), coarse);
-  // (the front pass made the pairs' fragment look-ups: k_mate_pairs skips them)
-  const uint64_t fmask_pairs = (nf && !fused) ? Tf - 1 : (uint64_t)0;
 
-  uint64_t Tm = mate_mode == 0 ? T : std::min<uint64_t>(T, table_size_for(std::min<uint64_t>(n, 4ull * n_tab + 1024)));
+  uint64_t Tm = fixed ? std::min<uint64_t>(T, table_size_for(std::min<uint64_t>(n, 4ull * n_tab + 1024))) : T;
   uint32_t e[4] = {0, 0, 0, 0};
-  bool listed = false;  // listed: the last pass of k_mate_pairs listed its table inserts (tab_list)
+  // aligner order with a few records on the table path: their inserts are listed and made by a dense pass (the front pass's counters,
+  // read back above, serve as the lists' lengths)
+  const bool listed = fixed && n_tab != 0;
   while (!fast) {
-    if (mate_mode != 2) ELP_HIP(c, hipMemsetAsync(table, 0xFF, Tm * sizeof(uint32_t), st));
+    ELP_HIP(c, hipMemsetAsync(table, 0xFF, Tm * sizeof(uint32_t), st));
     ELP_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(np_dev), (int)(uint32_t)nfixed, 1, st));
-    // aligner order with a few records on the table path: their inserts are listed and made by a dense pass (the counters of k_mate_scan,
-    // read back above, serve as the lists' lengths)
-    const bool defer_tab = mate_mode == 1 && n_tab != 0;
-    listed = defer_tab;
-    if (defer_tab) ELP_HIP(c, hipMemsetAsync(n_table_dev, 0, 64 * 16 * sizeof(uint32_t), st));
+    if (listed) ELP_HIP(c, hipMemsetAsync(n_table_dev, 0, 64 * 16 * sizeof(uint32_t), st));
     ELP_LAUNCH(c, "md_mate_pairs", k_mate_pairs, dim3(blocks_for(n, 256 * MP_R)), dim3(256), 0, m, (const uint4 *)fkey, code,
                (const uint32_t *)hash32, (const uint32_t *)hash_lo, (const uint32_t *)bloom, (uint32_t)(bw - 1), (const uint32_t *)(n_tab ? coarse : nullptr), table, Tm - 1, c->mate.p,
-               rep_of, c->err_flag.p,
-               (const uint32_t *)ftable, (const uint32_t *)fbits, fmask_pairs, best, mate_mode == 1 ? 1 : (mate_mode == 2 ? 2 : 0), pk, pv,
-               defer_tab ? tab_list : (uint32_t *)nullptr, n_table_dev, tab_cap);
-    if (defer_tab)  // (the lists hold the records k_mate_scan counted plus the neighbour pairs a filter hit sent along: in practice a fraction as many again)
+               rep_of, c->err_flag.p, fixed ? 1 : 0, pk, pv, listed ? tab_list : (uint32_t *)nullptr, n_table_dev, tab_cap);
+    if (listed)  // (the lists hold the records the front pass counted plus the neighbour pairs a filter hit sent along: in practice a fraction as many again)
       ELP_LAUNCH(c, "md_mate_table", k_mate_table, dim3(blocks_for(std::min<uint64_t>(n, 2ull * n_tab + 4096), 256)), dim3(256), 0, m, (const uint4 *)fkey, (const uint8_t *)code,
                  (const uint32_t *)hash32, (const uint32_t *)hash_lo, (const uint32_t *)tab_list, (const uint32_t *)n_table_dev, tab_cap, table, Tm - 1, c->mate.p, rep_of,
                  c->err_flag.p);
-    if (mate_mode == 2) {
-      int mbits = 0;
-      while (mbits < 24 && ((n + 1) >> mbits) > (uint64_t)MB_TARGET) mbits++;
-      const int mdig = (mbits + 7) / 8, msbits = 8 * mdig;
-      const size_t mnb = (size_t)1 << mbits;
-      uint32_t *ne_dev = c->md_ctr.p + 2, *mbounds;
-      ELP_TRY(scratch(c, 0, 2 * mnb + 8, &mbounds));  // (the table in HBM is not used in this mode)
-      ELP_HIP(c, hipMemsetAsync(ne_dev, 0, 4, st));
-      ELP_HIP(c, hipMemsetAsync(mbounds, 0, 2 * mnb * sizeof(uint32_t), st));
-      ELP_LAUNCH(c, "md_mate_list", k_mate_list, dim3(blocks_for(n, 256 * ML_TILES)), dim3(256), 0, n, (const uint8_t *)code, (const uint32_t *)hash32, pk, pv, ne_dev);
-      uint64_t *mks = pk;
-      uint32_t *mvs = pv;
-      if (mdig) {
-        ProfScope ps(c, "md_mate_");
-        ELP_TRY(radix_sort_pairs_low(c, pk, pv, pk + npmax, pv + npmax, n + 1, mdig, &mks, &mvs, nullptr, false, ne_dev));
-      }
-      ELP_LAUNCH(c, "md_mate_bounds", k_pair_bounds, dim3(blocks_for(n + 1, 256)), dim3(256), 0, (const uint64_t *)mks, (const uint32_t *)ne_dev, msbits, mbits, mbounds,
-                 mbounds + mnb);
-      ELP_LAUNCH(c, "md_mate_bucket", k_mate_bucket, dim3((unsigned)mnb), dim3(256), 0, m, (const uint4 *)fkey, (const uint64_t *)mks, (const uint32_t *)mvs, (const uint32_t *)mbounds,
-                 (const uint32_t *)(mbounds + mnb), c->mate.p, rep_of, c->err_flag.p);
-      // (`table` may have been re-pointed by the scratch call above: take it again for a fall-back pass)
-      ELP_TRY(scratch(c, 0, T, &table));
-    }
-    // tournament among the fragments of pair-free groups (the marks k_mate_pairs left in `best` are complete whatever the error words
-    // will say): queued in front of the read-back, so that the device works on it while the host waits
-    if (nf && !frag_done) {
-      ELP_LAUNCH(c, "md_frag_tie", k_frag_tie, dim3(fgrid), dim3(256), 0, m, (const uint32_t *)flist, nf, (const uint32_t *)rep,
-                 (const unsigned long long *)best, winner);
-      ELP_LAUNCH(c, "md_frag_flag", k_frag_flag, dim3(fgrid), dim3(256), 0, m, (const uint32_t *)flist, nf, (const uint32_t *)rep,
-                 (const unsigned long long *)best, (const uint32_t *)winner, c->flag.p);
-      frag_done = true;
-    }
     ELP_TRY(fetch_err(c, e));
-    if (mate_mode == 2 && (e[1] & 4u)) {
-      // a bucket's keys did not fit its LDS table (keys crafted to share hash bits): the table in HBM takes all candidates
-      mate_mode = 0;
-      Tm = T;
-    } else if (!(e[1] & 2u)) {
-      break;
-    } else {
-      if (Tm == T) return set_error(c, ELP_ERR_HIP, "mark duplicates: mate table overflow");
-      Tm = T;  // more Bloom-filter hits than estimated: once more with the full-size table (the look-ups and entries are simply made again)
-    }
+    if (!(e[1] & 2u)) break;
+    if (Tm == T) return set_error(c, ELP_ERR_HIP, "mark duplicates: mate table overflow");
+    Tm = T;  // more Bloom-filter hits than estimated: once more with the full-size table (the look-ups and entries are simply made again)
     ELP_HIP(c, hipMemsetAsync(c->err_flag.p + 1, 0, 4, st));
     ELP_HIP(c, hipMemsetAsync(c->mate.p, 0xFF, n * sizeof(uint32_t), st));
     ELP_HIP(c, hipMemsetAsync(rep_of, 0xFF, n * sizeof(uint32_t), st));
@@ -1413,7 +1083,7 @@ static int markdup_impl(elp_ctx *c) {
     const bool folded = ndig > 0;
     ELP_HIP(c, hipMemsetAsync(bounds, folded ? 0xFF : 0, 2 * nb * sizeof(uint32_t), st));
     // aligner order without stragglers: no record announced its key, so nothing went through the mate table - `rep_of` (pair_win's
-    // buffer) is still all EMPTY from its fill in front of the scan and no owner carries MC_TABBED: no second fill, no scan of the codes
+    // buffer) is still all EMPTY from the front pass and no owner carries MC_TABBED: no second fill, no scan of the codes
     const bool no_table = fixed && n_tab == 0 && !e[1];
     if (!no_table) {
       ELP_HIP(c, hipMemsetAsync(c->pair_win.p, 0xFF, n * sizeof(uint32_t), st));

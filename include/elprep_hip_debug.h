@@ -42,13 +42,11 @@ int elp_rollback(elp_ctx *ctx);
  *   "bgzf_piece"       inflated bytes per record-scan pass of elp_stage_bgzf (default 1 GiB)
  *   "bgzf_inflate_piece"  inflated bytes whose blocks one launch of the decoder takes (default 2 GiB; the scan passes of
  *                      "bgzf_piece" bytes run inside it; token scratch: 171 KB per 64 KB block)
- *   "bgzf_fixed"       1: elp_emit_sorted_bgzf writes fixed Huffman codes only (round 5) instead of the blocks' own codes
+ *   "bgzf_fixed"       1: elp_emit_sorted_bgzf writes fixed Huffman codes only instead of the blocks' own codes
  *   "bgzf_copy_chunk"  blocks per H2D chunk and decoder launch of elp_stage_bgzf (0: the blocks that fill the chip once);
  *   "bgzf_first_chunk_div"  the first chunk is 1/div of that (default 4: the decoder starts early)
  *   "bgzf_tok_fail_above"  (tests) the decoder's token scratch "does not fit" for more than this many blocks: the launch halves
  *   "bgzf_tok_lds"     (experiments) unused LDS bytes per decoder wave: fewer waves per CU
- *   "bgzf_inflate"     1: round 5's decoder (one kernel: a wave decodes and copies a block, window in LDS; separate CRC pass)
- *                      instead of round 6's two phases (tokens: 64 candidate symbols per wave and step; matches + CRC: a workgroup)
  *   "bgzf_weak_guess"  1: elp_stage_bgzf's blocks guess their first record start blindly (every guess is then repaired: same result)
  *   "score_kernel"     1: general Phred-score / low-quality-tail kernel even for read sets of one length
  *   "count3_rlog"      >= 0: log2 of the context-cell replication of the one-length count kernel (measurements)
@@ -59,15 +57,14 @@ int elp_rollback(elp_ctx *ctx);
  *   "presort_tile"     1 / 2 / 3: radix tile (4096 / 8192 / 16384 keys) of the key passes elp_sort_ahead queues from inside mark duplicates (default 2)
  *   "side_priority"    1: the side lanes' streams (sort, metrics) get the highest stream priority instead of the default - set before their first use
  *   "apply_wgs"        1 .. 3: workgroups per CU of the one-length ApplyBQSR kernel (default: what its LDS allows, at most 3)
- *   "md_fused"         1: mark duplicates by the separate passes of rounds 2-5 (adapt_fixed, md_keys, md_mate_scan, md_mate_pairs) instead of
- *                      the fused front pass of round 6 (md_front) - same flags; A/B timing and the tests run both
- *   "mate_path"        1: every mate candidate is matched by the partitioned pass (hash partition + LDS tables), no neighbour
- *                      shortcut - what coordinate-ordered or shuffled input takes by itself; 2: ... by the table in HBM
+ *   "mate_path"        2: every mate candidate of elp_mark_duplicates is matched by the table in HBM, no neighbour shortcut - the path
+ *                      coordinate-ordered or shuffled input takes by itself (0: the library decides; 1 is refused)
  *   "radix_tile"       1: every radix pass in tiles of 4096 keys; 2: of 8192 keys; 3: of 16384 (default: by the array's length)
  *   "sort_pairs"       1: the coordinate sort moves (key, index) pairs through its passes even where key << b | index fits one word
  *   "tie_rounds"       1: the coordinate sort orders its long runs of equal coordinates (the unmapped block, pile-ups) by radix rounds
  *                      over every live name position - the path a group of > 1024 names that agree in their leading positions takes
  *                      by itself - instead of one round on the leading positions + comparison of what it leaves equal
+ *   "md_fused", "bgzf_inflate"  retired: 0 is accepted and changes nothing, any other value is refused
  * Returns ELP_ERR_ARG for an unknown key or a value out of range. */
 int elp_set_tuning(elp_ctx *ctx, const char *key, int64_t value);
 

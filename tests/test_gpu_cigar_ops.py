@@ -271,10 +271,10 @@ def _check_coverage(b, h, refs, sites, meta):
 
 
 # kernel choices: every value of every key at least once with the ragged set and with a one-length set (four settings x two sets)
-TUNINGS = [dict(count_kernel=0, apply_kernel=0, score_kernel=0, md_fused=0, mate_path=0),
-           dict(count_kernel=1, apply_kernel=1, score_kernel=1, md_fused=1, mate_path=1),
-           dict(count_kernel=2, apply_kernel=3, score_kernel=0, md_fused=1, mate_path=2),
-           dict(count_kernel=3, apply_kernel=0, score_kernel=1, md_fused=0, mate_path=2)]
+TUNINGS = [dict(count_kernel=0, apply_kernel=0, score_kernel=0, mate_path=0),
+           dict(count_kernel=1, apply_kernel=1, score_kernel=1, mate_path=2),
+           dict(count_kernel=2, apply_kernel=3, score_kernel=0, mate_path=2),
+           dict(count_kernel=3, apply_kernel=0, score_kernel=1, mate_path=2)]
 
 
 @pytest.mark.parametrize("tune,length", [(t, 0) for t in range(len(TUNINGS))] + [(t, 150 if t % 2 == 0 else 151) for t in range(len(TUNINGS))])

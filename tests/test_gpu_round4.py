@@ -81,6 +81,17 @@ def test_set_tuning_rejects_unknown_keys_and_bad_values():
     with pytest.raises(ElpError, match="power of two"):
         e.set_tuning("pair_table_slots", 3)
     e.set_tuning("pair_table_slots", 64)
+    # retired keys (their paths are gone): 0 is still accepted, anything else fails loudly instead of measuring the default path
+    for key in ("md_fused", "bgzf_inflate"):
+        e.set_tuning(key, 0)
+        with pytest.raises(ElpError, match="retired") as err:
+            e.set_tuning(key, 1)
+        assert err.value.code == -1  # ELP_ERR_ARG
+    with pytest.raises(ElpError, match="mate_path") as err:
+        e.set_tuning("mate_path", 1)
+    assert err.value.code == -1
+    e.set_tuning("mate_path", 2)
+    e.set_tuning("mate_path", 0)
     e.close()
 
 
@@ -235,7 +246,6 @@ def _bgzf(stream: bytes, level: int, strategy: int = 0, cut: int = 65280, mem_le
     (6, 2, 65280, None),                                         # Z_HUFFMAN_ONLY: literals only, codes longer than the tables' bits
     (6, 3, 65280, None),                                         # Z_RLE: matches at distance 1 (a match that overlaps itself)
     (6, 1, 2111, {"mem_level": 3}),                              # Z_FILTERED, small members
-    (1, 0, 30011, {"bgzf_inflate": 1}),                          # round 5's one-kernel decoder stays available
     (6, 0, 4099, {"bgzf_tok_fail_above": 37}),                   # the token scratch "does not fit": the decoder's launches halve
 ])
 def test_stage_bgzf_gives_the_records_of_stage_bam(level, strategy, cut, tuning):
@@ -372,11 +382,11 @@ def test_count_split_by_covariate(n_cov, n_q, length):
         e.close()
 
 
-@pytest.mark.parametrize("mate_path", [0, 1, 2])
+@pytest.mark.parametrize("mate_path", [0, 2])
 def test_mates_by_every_path(mate_path):
-    """the neighbour shortcut (0, aligner order), the partitioned pass (1: hash partition + LDS tables, what shuffled input takes) and the
-    table in HBM (2) pair the same records: aligner order, shuffled order, and the DeleteOrStore toggling cases with three and four records
-    per QNAME (the arrival-order pairing of big groups) - flags, counters and set-size histograms against the oracle"""
+    """the library's own choice (0: the neighbour shortcut in aligner order, the table in HBM for shuffled input) and the table in HBM for
+    every candidate (2) pair the same records: aligner order, shuffled order, and the DeleteOrStore toggling cases with three and four
+    records per QNAME (the arrival-order pairing of big groups) - flags, counters and set-size histograms against the oracle"""
     from tests import kat_cases
     from elprep_amd.batch import Batch
     tune = {"mate_path": mate_path}

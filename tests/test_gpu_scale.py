@@ -223,8 +223,9 @@ def _production_step(e, h):
 
 
 def test_full_size_whole_path_against_the_oracle(c3):
-    """Pass A: the production step.  Pass B, after rollback: the general flat count / apply / score kernels, the unfused mark-duplicates
-    front and the (key, index) pair sort, in the serial order with the dense LUT.  Then the queryname sort and a coordinate sort behind it."""
+    """Pass A: the production step.  Pass B, after rollback: the general flat count / apply / score kernels, the sort-first adapt stage
+    (mark duplicates behind it: the front pass without its adapt part) and the (key, index) pair sort, in the serial order with the dense
+    LUT.  Then the queryname sort and a coordinate sort behind it."""
     from tools.prof.qname_sort_speed import _check, _name_rows
     b, h, o = c3.b, c3.h, c3.o
     _preconditions(b)
@@ -246,20 +247,22 @@ def test_full_size_whole_path_against_the_oracle(c3):
         # kernel's name, bqsr_apply); the coordinate sort in its word form (the pair form's passes are booked as sort_pairs_*)
         for k in ("md_front", "adapt_score", "bqsr_seg_offsets", "bqsr_apply", "radix_scatter"):
             assert k in ran, "pass A did not launch " + k
-        for k in ("md_keys", "adapt_score_flat", "bqsr_apply_records", "sort_pairs_radix_scatter"):
+        for k in ("adapt_fixed", "adapt_score_flat", "bqsr_apply_records", "sort_pairs_radix_scatter"):
             assert k not in ran, "pass A launched " + k
         _expect_path("pass A", e, o, b.qual_off, ctr, e.tables_fetch())
         _log("pass A equal")
 
-        # pass B.  rollback() clears the context's adapted state, and set_tuning("score_kernel") clears it again: mark duplicates below runs
-        # the adapt stage (and with it the score kernel) anew, now with the flat kernel (adapt_score_flat).  The pair sort's passes are
-        # booked as sort_pairs_*; count_kernel=1 shows as the missing count3 segment offsets.  The flat apply kernel and apply3 both launch
-        # as bqsr_apply: the profile shows only that apply3's own record kernel did not run.
+        # pass B.  rollback() clears the context's adapted state, and set_tuning("score_kernel") clears it again: the first sort below runs
+        # the adapt stage (adapt_fixed, and the score kernel) anew, now with the flat kernel (adapt_score_flat), and mark duplicates then
+        # takes the front pass without the adapt part; the sort behind mark duplicates is the one that is checked.  The pair sort's passes
+        # are booked as sort_pairs_*; count_kernel=1 shows as the missing count3 segment offsets.  The flat apply kernel and apply3 both
+        # launch as bqsr_apply: the profile shows only that apply3's own record kernel did not run.
         e.rollback()
-        for k in ("count_kernel", "apply_kernel", "score_kernel", "md_fused", "sort_pairs"):
+        for k in ("count_kernel", "apply_kernel", "score_kernel", "sort_pairs"):
             e.set_tuning(k, 1)
         e.sort_ahead(False)
         e.profile_reset()
+        e.sort_coordinate(fetch=False)
         e.mark_duplicates(True, fetch=False)
         e.sort_coordinate(fetch=False)
         ctr = e.dup_metrics(100)
@@ -270,9 +273,9 @@ def test_full_size_whole_path_against_the_oracle(c3):
         ran = _launched(e)
         e.profile_enable(False)
         _log("pass B kernels: %s" % sorted(ran))
-        for k in ("md_keys", "adapt_fixed", "adapt_score_flat", "bqsr_count", "bqsr_apply", "sort_pairs_radix_scatter"):
+        for k in ("md_front", "adapt_fixed", "adapt_score_flat", "bqsr_count", "bqsr_apply", "sort_pairs_radix_scatter"):
             assert k in ran, "pass B did not launch " + k
-        for k in ("md_front", "adapt_score", "bqsr_seg_offsets", "bqsr_apply_records"):
+        for k in ("adapt_score", "bqsr_seg_offsets", "bqsr_apply_records"):
             assert k not in ran, "pass B launched " + k
         _expect_path("pass B", e, o, b.qual_off, ctr, tables)
         _log("pass B equal")

@@ -1,4 +1,5 @@
-"""mark duplicates on reads staged in random order (mates are not neighbours): the partitioned mate pass against the table in HBM.
+"""mark duplicates on reads staged in random order (mates are not neighbours): the library's own choice (mate_path 0) against every
+candidate through the table in HBM (mate_path 2).
 usage: shuffled_md.py [reads]"""
 import sys
 import time
@@ -17,7 +18,7 @@ parts = []
 for lo in range(0, reads // 2, 1_000_000):
     b = synth.generate(cfg, lo, min(lo + 1_000_000, reads // 2))
     parts.append(b.take(rng.permutation(b.n)))
-for path in (0, 2, 1):
+for path in (0, 2):
     e = Engine(h, tuning={"mate_path": path})
     for p in parts:
         e.stage(p)
