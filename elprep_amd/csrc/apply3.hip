@@ -505,7 +505,7 @@ int apply3_launch(elp_ctx *c, int max_cycle, const uint8_t *d_lut, const uint8_t
                (const uint16_t *)c->rg_cov.p, (const uint64_t *)c->qbounds.p, d_cov_present, (const uint32_t *)blk, cw + 2 * A3_MAXCOV + 1, recs, ridx, c->err_flag.p);
   }
   // the adapt stage's score kernel left the records (same length, same lmax: both are the one length of the staged reads)
-  const bool adapt_recs = !split && c->adapted && c->apply_recs_valid && c->apply_recs_lmax == lmax && c->apply_recs.cap >= n;
+  const bool adapt_recs = !split && c->derived.scores && c->derived.apply_recs_valid && c->apply_recs_lmax == lmax && c->apply_recs.cap >= n;
   if (!split && !adapt_recs)
     ELP_LAUNCH(c, "bqsr_apply_records", k_apply_records, dim3(blocks_for(n, 256)), dim3(256), 0, n, len, lmax, (const uint16_t *)c->flag.p,
                (const uint16_t *)c->rgid.p, (const uint16_t *)c->rg_cov.p, (const uint64_t *)c->qbounds.p, d_cov_present, recs, c->err_flag.p);

@@ -459,11 +459,7 @@ int elp_stage_bam(elp_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint
   hipStream_t st = c->stream;
   // pieces are committed one at a time: whatever was derived from the records staged so far is invalid from here on, also if a later
   // piece fails
-  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
-  c->have_qual_present = false;
-  c->have_snapshot = false;
-  c->flat_index_n = 0;
-  c->uniform_n = ~0ull;
+  c->derived.records_changed();
   if (!c->copy_stream) ELP_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
   // is the caller's buffer page-locked (elp_pinned_alloc / hipHostRegister)?  then the DMA engine reads it directly
   hipPointerAttribute_t pa;
@@ -532,11 +528,7 @@ int elp_stage_bam(elp_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint
     at_byte = p;
   }
   ELP_HIP(c, elp::stream_wait(st));
-  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
-  c->have_qual_present = false;
-  c->have_snapshot = false;
-  c->flat_index_n = 0;
-  c->uniform_n = ~0ull;
+  c->derived.records_changed();
   return 0;
 }
 
@@ -611,7 +603,7 @@ static BamOut bam_out_of(const elp_ctx *c) {
 int elp_emit_sorted_bam(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
   if (!c || !n_bytes_out) return ELP_ERR_ARG;
   ELP_HIP(c, hipSetDevice(c->device));
-  if (!c->sorted) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bam: call elp_sort_coordinate or elp_sort_queryname first");
+  if (!c->derived.sorted) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bam: call elp_sort_coordinate or elp_sort_queryname first");
   ELP_TRY(radix_check(c));
   if (c->raw_n != c->n) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bam: records were not staged with elp_stage_bam");
   const BamOut m = bam_out_of(c);
@@ -626,7 +618,7 @@ int elp_emit_sorted_bam(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_byte
 int elp_emit_sorted_bgzf(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
   if (!c || !n_bytes_out) return ELP_ERR_ARG;
   ELP_HIP(c, hipSetDevice(c->device));
-  if (!c->sorted) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bgzf: call elp_sort_coordinate or elp_sort_queryname first");
+  if (!c->derived.sorted) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bgzf: call elp_sort_coordinate or elp_sort_queryname first");
   ELP_TRY(radix_check(c));
   if (c->raw_n != c->n) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bgzf: records were not staged with elp_stage_bam");
   const BamOut m = bam_out_of(c);
@@ -649,7 +641,7 @@ __global__ __launch_bounds__(256) void k_merge_fill(uint64_t n_out, const uint32
 
 int elp_emit_merged_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
   if (!groups || !spread || groups == spread || !n_bytes_out) return ELP_ERR_ARG;
-  if (groups->sorted_qname || spread->sorted_qname) return merge_refuses_queryname(groups, "elp_emit_merged_bam");
+  if (groups->derived.sorted_qname || spread->derived.sorted_qname) return merge_refuses_queryname(groups, "elp_emit_merged_bam");
   if (groups->raw_n != groups->n || spread->raw_n != spread->n) return set_error(groups, ELP_ERR_ARG, "elp_emit_merged_bam: records were not staged with elp_stage_bam");
   uint64_t *slots = nullptr;
   ELP_TRY(merge_spread_slots(groups, spread, &slots));  // checks: both sorted, one device

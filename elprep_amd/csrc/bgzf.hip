@@ -1061,11 +1061,7 @@ extern "C" int elp_stage_bgzf(elp_ctx *c, const uint8_t *bgzf, uint64_t n_bytes,
   }
   (void)saw_eof;  // (the end-of-file block is the host's to insist on: a caller may hand over a file in several calls)
   if (first_record > inflated) return set_error(c, ELP_ERR_ARG, "elp_stage_bgzf: first_record lies behind the inflated data");
-  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
-  c->have_qual_present = false;
-  c->have_snapshot = false;
-  c->flat_index_n = 0;
-  c->uniform_n = ~0ull;
+  c->derived.records_changed();
   if (blocks.empty()) return 0;
   hipStream_t st = c->stream;
   static const CrcPow pw = crc_pow_table();

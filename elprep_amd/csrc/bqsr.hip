@@ -1859,7 +1859,7 @@ static int gather_impl(elp_ctx *c, int max_cycle, int64_t *qual_tbl, int64_t *cy
       if (!(e[0] & 128u)) break;
       // a counted base had a quality the sampled hint did not contain: take the exact set (full scan) and redo the count
       ELP_HIP(c, hipMemsetAsync(c->err_flag.p, 0, 4, st));
-      c->have_qual_present = false;
+      c->derived.qual_hint_refuted();
       ELP_TRY(ensure_qual_present(c, true));
       if (attempt >= 2) return set_error(c, ELP_ERR_HIP, "BQSR: quality-slot retry did not converge");
       ELP_HIP(c, hipMemsetAsync(tb, 0, (nq + nc + nx) * sizeof(unsigned long long), st));
@@ -2134,7 +2134,7 @@ int elp_bqsr_lut_upload(elp_ctx *c, int max_cycle, const uint8_t *lut, const uin
 static int lut_uploaded(elp_ctx *c, int max_cycle) {
   c->dict_ready = false;
   const bool force_old = c->tune.apply_kernel == 1;
-  if (!force_old && c->have_qual_present && c->uniform_n == c->n && c->uniform_len >= 16 && c->n > 0 && (int64_t)c->max_l_seq <= (int64_t)max_cycle) {
+  if (!force_old && c->derived.have_qual_present && c->derived.uniform_n == c->n && c->uniform_len >= 16 && c->n > 0 && (int64_t)c->max_l_seq <= (int64_t)max_cycle) {
     int qlo, qhi;
     lut_quality_range(c, &qlo, &qhi);
     const int lmax = (int)std::max<uint32_t>(c->max_l_seq, 1);
@@ -2280,8 +2280,7 @@ static int bqsr_apply_impl(elp_ctx *c, int max_cycle, const uint8_t *lut, const 
         ELP_TRY(fetch_err(c, e3));
         if ((e3[0] & ~512u) != 0) return bqsr_error(c, e3[0] & ~512u);
         if (!(e3[0] & 512u)) {
-          c->adapted = false;
-          c->have_qual_present = false;
+          c->derived.qual_changed();
           return 0;
         }
         ELP_HIP(c, hipMemsetAsync(c->err_flag.p, 0, 4, c->stream));
@@ -2331,8 +2330,7 @@ static int bqsr_apply_impl(elp_ctx *c, int max_cycle, const uint8_t *lut, const 
   uint32_t e[4];
   ELP_TRY(fetch_err(c, e));
   if (e[0]) return bqsr_error(c, e[0]);
-  c->adapted = false;  // scores depend on QUAL
-  c->have_qual_present = false;
+  c->derived.qual_changed();  // (the scores and the quality hint; the keys do not read QUAL)
   return 0;
 }
 

@@ -17,6 +17,7 @@
 
 #include "../../include/elprep_hip.h"
 #include "../../include/elprep_hip_debug.h"
+#include "derived.hpp"
 
 namespace elp {
 
@@ -100,24 +101,17 @@ struct elp_ctx {
   uint32_t max_pos = 0;  // largest staged POS (as uint32): width of the POS field of the coordinate-sort key
   int key_bits = 64;     // live low bits of the coordinate-sort key column (set with it, ensure_adapted)
 
-  // derived state
-  bool adapted = false, sorted = false, marked = false;
-  bool sorted_qname = false;  // the permutation (sorted) is in queryname order (elp_sort_queryname, qsort.hip), not coordinate order
+  // derived data; which of it is valid for the staged records: `derived` (derived.hpp)
+  elp::Derived derived;
   bool radix_check_pending = false;  // radix passes were queued whose look-back timeout bit nobody has read yet (fetch_err)
-  bool adapt_bad_qual = false;  // adapt_score met a quality > 93 in a duplicate-marking candidate
-  bool adapt_pending = false;   // ... or may have: its error word (adapt_err) has not been read yet
   elp::DVec<uint32_t> adapt_err;  // [0] the score kernel's error word, [2 .. 5] the quality values k_score_uniform's sampled groups saw
-  bool adapt_sampled = false;      // the score kernel of this adapt stage sampled the quality values ...
-  bool adapt_qmask_valid = false;  // ... and they have been read (adapt_note)
   unsigned long long adapt_qmask[2] = {0, 0};
-  elp::DVec<uint2> apply_recs;     // ApplyBQSR's per-read records (apply_rec.hpp), written by k_score_uniform ...
-  bool apply_recs_valid = false;   // ... of this adapt stage, for reads of apply_recs_lmax bases
+  elp::DVec<uint2> apply_recs;     // ApplyBQSR's per-read records (apply_rec.hpp), written by k_score_uniform for reads of apply_recs_lmax bases
   int apply_recs_lmax = 0;
-  bool have_qual_present = false;
   unsigned long long qual_present[2] = {0, 0};  // bit q set if quality value q was seen in a sample of the QUAL column (sizing hint for the BQSR tables)
   elp::DVec<int32_t> upos, score;
   elp::DVec<uint64_t> qbounds;  // per record: 1 + index of the last quality > 2 (low 32 bits; 0 = none) and index of the first one (high): the
-                                // low-quality-tail bounds of computeStrandedClippedSeq (bqsr.go:316-332) on the full read; valid when adapted
+                                // low-quality-tail bounds of computeStrandedClippedSeq (bqsr.go:316-332) on the full read; valid with the scores
   elp::DVec<uint64_t> key;      // coordinate sort keys, staging order
   elp::DVec<uint32_t> perm;     // sorted position -> staging index
   elp::DVec<uint32_t> err_flag; // device-side error word(s)
@@ -138,9 +132,7 @@ struct elp_ctx {
   static constexpr uint32_t MAX_QNAME = 1000; // staged QNAME length limit; the comparator string (QNAME + 15 bytes) fits TIE_LIVE_WORDS * 32 bits
   static constexpr uint32_t TIE_LIVE_WORDS = 32;
   uint32_t radix_epoch = 0;
-  uint64_t flat_index_n = 0, flat_index_bytes = 0;
   uint32_t uniform_len = 0;  // > 0: every staged read has this many bases and the offset columns are arithmetic (ensure_uniform_len)
-  uint64_t uniform_n = ~0ull, uniform_bytes = ~0ull;
 
   // mark-duplicates results kept for the metrics pass
   elp::DVec<uint32_t> mate;        // per record: staging index of its mate if the two form a pair (classifyPair), else 0xFFFFFFFF
@@ -225,16 +217,14 @@ struct elp_ctx {
   // elp_mark_duplicates queues them on the sort lane the moment its front pass has written the keys (no host wait involved), and they run
   // under the pair phase; elp_sort_coordinate then finds the sorted words and only breaks the ties (which see the final FLAGs)
   bool sort_ahead = false;
-  uint64_t adapt_epoch = 0;          // counts the writes of the key column (adapt_begin)
-  uint64_t presort_epoch = ~0ull, presort_n = 0;
-  uint64_t *presort_ks = nullptr;    // the sorted words, in the sort lane's scratch slot 0 (valid while presort_epoch == adapt_epoch)
+  uint64_t presort_n = 0;
+  uint64_t *presort_ks = nullptr;    // the sorted words, in the sort lane's scratch slot 0 (valid while derived.presorted)
   int presort_idx_bits = 0;
 
   // snapshot of the mutable columns
   elp::DVec<uint16_t> snap_flag;
   elp::DVec<uint8_t> snap_qual;
   uint64_t snap_n = 0, snap_qual_bytes = 0;
-  bool have_snapshot = false;
 
   // elp_set_tuning: kernel choices a caller (tests, A/B measurements) can pin; 0 = the library decides
   struct Tuning {
@@ -475,10 +465,12 @@ int radix_sort_pairs_low(elp_ctx *c, uint64_t *keys, uint32_t *vals, uint64_t *k
                          uint64_t **keys_out, uint32_t **vals_out, const uint64_t *first_src = nullptr, bool identity_vals = false,
                          const uint32_t *n_dev = nullptr /* the length is *n_dev on the device and `n` its upper bound */, RadixBounds bnd = RadixBounds{});
 int exclusive_scan_u32(elp_ctx *c, const uint32_t *in, uint32_t *out, uint64_t n, uint32_t *total_host /* may be null */);
-int ensure_adapted(elp_ctx *c, bool check_quals = true);
+int ensure_adapted(elp_ctx *c, bool check_quals = true);  // sort.hip: keys and scores valid (the whole adapt stage if either is missing)
+int ensure_keys(elp_ctx *c);                               // sort.hip: the keys valid - all the coordinate sort asks for
 // the two halves of ensure_adapted for a caller that computes the fixed-field part (unclipped positions, sort keys) itself - mark
-// duplicates' front pass, markdup.hip: adapt_begin = buffers, key width (*pos_bits), the error word's fill; adapt_scores = the score kernel
-// (every record's score and low-quality-tail bounds).  The caller sets c->adapted once its own pass is queued.
+// duplicates' front pass, markdup.hip: adapt_begin = buffers, key width (*pos_bits), the error word's fill, derived.adapt_begins();
+// adapt_scores = the score kernel (every record's score and low-quality-tail bounds).  The caller sets c->derived.keys and
+// c->derived.scores once its own pass is queued.
 int adapt_begin(elp_ctx *c, int *pos_bits);
 int adapt_scores(elp_ctx *c);
 int mailbox(elp_ctx *c);  // ctx.hip: c->mail (1024 words, page-locked) and c->mail_ev exist

@@ -165,8 +165,7 @@ int fetch_err(elp_ctx *c, uint32_t *words) {
     const uint32_t w0 = words[0] & ~256u;
     ELP_HIP(c, hipMemcpyAsync(c->err_flag.p, &w0, 4, hipMemcpyHostToDevice, c->stream));
     ELP_HIP(c, elp::stream_wait(c->stream));
-    c->sorted = c->sorted_qname = false;
-    c->marked = false;
+    c->derived.radix_timed_out();
     return set_error(c, ELP_ERR_HIP, "radix sort: tile look-back timed out");
   }
   return 0;
@@ -320,7 +319,7 @@ int elp_set_header(elp_ctx *c, const elp_header *h) {
     return set_error(c, ELP_ERR_ARG, "elp_set_header: bad arguments");
   ELP_HIP(c, hipSetDevice(c->device));
   c->n_ref = h->n_ref; c->n_rg = h->n_rg; c->n_lib = h->n_lib; c->n_cov = h->n_cov;
-  c->apply_recs_valid = false;  // (they hold the read groups' covariates)
+  c->derived.header_changed();  // (ApplyBQSR's records hold the read groups' covariates)
   c->h_ref_len.assign(h->ref_len, h->ref_len + h->n_ref);
   c->h_rg_lib.assign(h->rg_lib, h->rg_lib + h->n_rg);
   c->h_rg_cov.assign(h->rg_cov, h->rg_cov + h->n_rg);
@@ -396,11 +395,7 @@ int elp_reset(elp_ctx *c) {
   c->max_split = 0;
   c->max_qname_len = c->max_l_seq = 0;
   c->max_pos = 0;
-  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
-  c->have_qual_present = false;
-  c->have_snapshot = false;
-  c->flat_index_n = 0;
-  c->uniform_n = ~0ull;
+  c->derived.records_changed();
   return 0;
 }
 
@@ -483,11 +478,7 @@ int elp_stage(elp_ctx *c, const elp_batch *b) {
   c->n_sr += n_sr;
   c->max_split = max_split;
   c->max_qname_len = max_qname_len; c->max_l_seq = max_l_seq; c->max_pos = max_pos;
-  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
-  c->have_qual_present = false;
-  c->have_snapshot = false;
-  c->flat_index_n = 0;
-  c->uniform_n = ~0ull;
+  c->derived.records_changed();
   return 0;
 }
 
@@ -525,7 +516,7 @@ static int d2h(elp_ctx *c, void *dst, const void *src, size_t bytes) {
 
 int elp_get_permutation(elp_ctx *c, uint32_t *out) {
   if (!c || (!out && c->n)) return ELP_ERR_ARG;
-  if (!c->sorted) return set_error(c, ELP_ERR_ARG, "elp_get_permutation: call elp_sort_coordinate or elp_sort_queryname first");
+  if (!c->derived.sorted) return set_error(c, ELP_ERR_ARG, "elp_get_permutation: call elp_sort_coordinate or elp_sort_queryname first");
   ELP_TRY(radix_check(c));
   return d2h(c, out, c->perm.p, c->n * sizeof(uint32_t));
 }
@@ -555,18 +546,17 @@ int elp_snapshot(elp_ctx *c) {
   if (c->qual_bytes) ELP_HIP(c, hipMemcpyAsync(c->snap_qual.p, c->qual.p, c->qual_bytes, hipMemcpyDeviceToDevice, c->stream));
   c->snap_n = c->n;
   c->snap_qual_bytes = c->qual_bytes;
-  c->have_snapshot = true;
+  c->derived.have_snapshot = true;
   return 0;
 }
 int elp_rollback(elp_ctx *c) {
   if (!c) return ELP_ERR_ARG;
-  if (!c->have_snapshot || c->snap_n != c->n || c->snap_qual_bytes != c->qual_bytes)
+  if (!c->derived.have_snapshot || c->snap_n != c->n || c->snap_qual_bytes != c->qual_bytes)
     return set_error(c, ELP_ERR_ARG, "elp_rollback: no snapshot of the current record set");
   ELP_HIP(c, hipSetDevice(c->device));
   if (c->n) ELP_HIP(c, hipMemcpyAsync(c->flag.p, c->snap_flag.p, c->n * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->stream));
   if (c->qual_bytes) ELP_HIP(c, hipMemcpyAsync(c->qual.p, c->snap_qual.p, c->qual_bytes, hipMemcpyDeviceToDevice, c->stream));
-  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
-  c->have_qual_present = false;
+  c->derived.flag_qual_restored();
   return 0;
 }
 
@@ -578,10 +568,10 @@ int elp_set_tuning(elp_ctx *c, const char *key, int64_t value) {
   else if (k == "apply_kernel") c->tune.apply_kernel = v;
   else if (k == "bgzf_piece") { if (value < 1) return set_error(c, ELP_ERR_ARG, "elp_set_tuning: bgzf_piece must be positive"); c->tune.bgzf_piece = value; }
   else if (k == "bgzf_weak_guess") c->tune.bgzf_weak_guess = v;
-  else if (k == "score_kernel") { c->tune.score_kernel = v; c->adapted = false; }
+  else if (k == "score_kernel") { c->tune.score_kernel = v; c->derived.score_tuning_changed(); }
   else if (k == "count3_rlog") c->tune.count3_rlog = v;
-  else if (k == "qual_hint") { c->tune.qual_hint = v; c->have_qual_present = false; }
-  else if (k == "qual_hint_drop") { c->tune.qual_hint_drop = v; c->have_qual_present = false; }
+  else if (k == "qual_hint") { c->tune.qual_hint = v; c->derived.hint_tuning_changed(); }
+  else if (k == "qual_hint_drop") { c->tune.qual_hint_drop = v; c->derived.hint_tuning_changed(); }
   else if (k == "pair_table_slots") {
     if (v == 0) { c->tune.pair_table_slots = 1 << 20; return 0; }
     if (v < 2 || v > (1 << 20) || (v & (v - 1))) return set_error(c, ELP_ERR_ARG, "elp_set_tuning: pair_table_slots must be a power of two >= 2");

@@ -241,11 +241,7 @@ static int append_piece(elp_ctx *dst, elp_ctx *from, const Gathered &G, uint64_t
   dst->max_qname_len = std::max(dst->max_qname_len, hc[XC_QNAME]);
   dst->max_l_seq = std::max(dst->max_l_seq, hc[XC_LSEQ]);
   dst->max_pos = std::max(dst->max_pos, hc[XC_POS]);
-  dst->adapted = dst->sorted = dst->sorted_qname = dst->marked = false;
-  dst->have_qual_present = false;
-  dst->have_snapshot = false;
-  dst->flat_index_n = 0;
-  dst->uniform_n = ~0ull;
+  dst->derived.records_changed();
   return 0;
 }
 

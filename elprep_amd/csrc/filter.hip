@@ -140,8 +140,8 @@ int merge_refuses_queryname(elp_ctx *groups, const char *who) {
 // MergeSortedFilesSplitPerChromosome's order as ranks, on the device: slots[j] = output slot of the j-th record of `spread`'s sorted output
 // among `groups`' sorted output (scratch slot 5 of `groups`; valid until that slot is reused).  Queued on groups->stream.
 int merge_spread_slots(elp_ctx *groups, elp_ctx *spread, uint64_t **slots_out) {
-  if (groups->sorted_qname || spread->sorted_qname) return merge_refuses_queryname(groups, "elp_merge_spread");
-  if (!groups->sorted || !spread->sorted) return set_error(groups, ELP_ERR_ARG, "elp_merge_spread: both contexts must be coordinate-sorted");
+  if (groups->derived.sorted_qname || spread->derived.sorted_qname) return merge_refuses_queryname(groups, "elp_merge_spread");
+  if (!groups->derived.sorted || !spread->derived.sorted) return set_error(groups, ELP_ERR_ARG, "elp_merge_spread: both contexts must be coordinate-sorted");
   if (groups->device != spread->device) return set_error(groups, ELP_ERR_ARG, "elp_merge_spread: contexts on different devices");
   ELP_HIP(groups, hipSetDevice(groups->device));
   // (a sort defers the read of its radix passes' look-back timeout bit: nothing is merged from a permutation that was flagged wrong)
@@ -304,7 +304,7 @@ extern "C" int elp_clean_sam(elp_ctx *c, uint64_t *n_clipped_out) {
   ELP_HIP(c, hipMemcpyAsync(hr, res, 8, hipMemcpyDeviceToHost, st));
   ELP_HIP(c, elp::stream_wait(st));
   // MAPQ changed, CIGARs may: whatever was derived from them is stale
-  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
+  c->derived.fixed_fields_changed();
   if (hr[1] & 1u) return set_error(c, ELP_ERR_DATA, "Unexpected non-0 relative clipping position in CleanSam. (reference: log.Panic, filters/utils.go:93)");
   if (hr[1] & 2u) return set_error(c, ELP_ERR_UNSUPPORTED, "elp_clean_sam: a clipped CIGAR needs an operation length outside the 28 bits of a BAM CIGAR field");
   ELP_LAUNCH(c, "clean_mapq", k_clean_mapq, dim3(blocks_for(n, 256)), dim3(256), 0, n, (const uint16_t *)c->flag.p, (const uint8_t *)c->has_sr.p, c->mapq.p);
@@ -380,7 +380,7 @@ int elp_filter_records(elp_ctx *c, const elp_predicates *p, uint64_t *n_dropped_
   }
   c->n_sr += dropped;  // they leave the output like the tagged copies do
   c->n_filtered += dropped + dropped_tagged;  // state-2 records of either origin: none of them is a duplicate-marking candidate
-  c->adapted = c->sorted = c->sorted_qname = c->marked = false;
+  c->derived.fixed_fields_changed();  // (the has_sr column)
   if (n_dropped_out) *n_dropped_out = dropped;
   return 0;
 }
@@ -424,7 +424,7 @@ int elp_split_classify(elp_ctx *c, const int32_t *group_of_ref, int32_t n_groups
                (const int32_t *)c->next_refid.p, (const int32_t *)d_gof, c->n_ref, n_groups, d_split, d_spread, d_cnt, c->split.p);
     // the split ids are part of every duplicate-marking key; records with equal keys share their contig, hence their split: no result changes
     c->max_split = std::max<uint32_t>(c->max_split, (uint32_t)n_groups);
-    c->marked = false;
+    c->derived.split_changed();
     if (split_out) ELP_HIP(c, hipMemcpyAsync(split_out, d_split, n * 2, hipMemcpyDeviceToHost, c->stream));
     if (spread_out) ELP_HIP(c, hipMemcpyAsync(spread_out, d_spread, n, hipMemcpyDeviceToHost, c->stream));
   }

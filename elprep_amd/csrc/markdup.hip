@@ -915,10 +915,10 @@ static int markdup_impl(elp_ctx *c) {
   const uint64_t n = c->n;
   ELP_TRY(ensure(c, c->mate, n + 1));
   ELP_TRY(ensure(c, c->pair_win, n + 1));
-  if (n == 0) { ELP_TRY(ensure_adapted(c, true)); c->marked = true; return 0; }
+  if (n == 0) { ELP_TRY(ensure_adapted(c, true)); c->derived.marked = true; return 0; }
   // the front pass also does the adapt stage's fixed-field part when that has not run yet (what a host that marks duplicates first - the
   // reference's order, cmd/filter.go:142-211 - gets)
-  const bool fuse_adapt = !c->adapted;
+  const bool fuse_adapt = !c->derived.adapted();  // (keys or scores missing: the fused pass writes both)
   int pos_bits = 1;
   if (fuse_adapt) ELP_TRY(adapt_begin(c, &pos_bits));
   else ELP_TRY(ensure_adapted(c, false));  // (its quality-error word is read with this call's first read-back, below)
@@ -999,7 +999,7 @@ static int markdup_impl(elp_ctx *c) {
     ELP_LAUNCH(c, "md_front", k_md_front<false>, dim3(blocks_for(n, MF_RECS)), dim3(MF_THREADS), 0, fc, (const int32_t *)c->score.p, c->upos.p, c->key.p, fkey, code, hash32, hash_lo, bloom,
                (uint32_t)(bw - 1), n_table_dev, (const uint32_t *)ftable, (const uint32_t *)fbits, nf ? Tf - 1 : (uint64_t)0, best, c->mate.p, c->pair_win.p, pk, pv,
                np_dev, nfx, optimistic);
-  if (fuse_adapt) c->adapted = true;
+  if (fuse_adapt) c->derived.keys = c->derived.scores = true;
   // elp_sort_ahead: the keys exist - the coordinate sort's key passes go to the sort lane now and run under the pair phase
   ELP_TRY(sort_presort(c));
   // tournament among the fragments of pair-free groups (the pair bits are complete): queued in front of the read-back
@@ -1012,11 +1012,11 @@ static int markdup_impl(elp_ctx *c) {
   // the table only has to hold the records that are not exactly-two-neighbours (few in aligner order) plus the neighbour pairs a
   // Bloom-filter hit sends there (at most as many again, in practice a fraction): size it by their number, not by n
   ELP_HIP(c, hipMemcpyAsync(n_tab64, n_table_dev, sizeof n_tab64, hipMemcpyDeviceToHost, st));
-  const bool adapt_read = c->adapt_pending;
+  const bool adapt_read = c->derived.adapt_pending;
   if (adapt_read) ELP_HIP(c, hipMemcpyAsync(adapt_word, c->adapt_err.p, sizeof adapt_word, hipMemcpyDeviceToHost, st));
   ELP_HIP(c, elp::stream_wait(st));
   if (adapt_read) adapt_note(c, adapt_word);
-  if (c->adapt_bad_qual) return adapt_quality_error(c);  // computePhredScore panics on such a record (filters/mark-duplicates.go:64-66)
+  if (c->derived.adapt_bad_qual) return adapt_quality_error(c);  // computePhredScore panics on such a record (filters/mark-duplicates.go:64-66)
   for (int k = 0; k < 64; k++) n_tab += n_tab64[k * 16];
 
   // aligner order (few candidates need a table): the neighbour pairs' entries go to fixed slots, the table's pairs behind them.  Else
@@ -1109,7 +1109,7 @@ static int markdup_impl(elp_ctx *c) {
                folded ? 1 : 0);
   }
   c->radix_check_pending = true;
-  c->marked = true;
+  c->derived.marked = true;
   return 0;
 }
 
@@ -1119,6 +1119,6 @@ extern "C" int elp_mark_duplicates(elp_ctx *c, int also_opticals) {
   (void)also_opticals;  // LIBID is derived from rgid on demand for every read
   if (!c) return ELP_ERR_ARG;
   ELP_HIP(c, hipSetDevice(c->device));
-  c->marked = false;
+  c->derived.drop_marked();
   return elp::markdup_impl(c);
 }

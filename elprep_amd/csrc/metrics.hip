@@ -505,7 +505,7 @@ __global__ __launch_bounds__(256) void k_origin_count(MxCols m, unsigned long lo
 static int metrics_impl(elp_ctx *c, int dist, int64_t *counters_host, int64_t *hist_host, int hist_len) {
   const uint64_t n = c->n;
   const int ncell = (c->n_lib + 1) * ELP_NCTR;
-  if (!c->marked) return set_error(c, ELP_ERR_ARG, "elp_dup_metrics: call elp_mark_duplicates first");
+  if (!c->derived.marked) return set_error(c, ELP_ERR_ARG, "elp_dup_metrics: call elp_mark_duplicates first");
   // device block: the counters, then (if asked for) the origins per library and the three histograms per library
   const size_t nhist = hist_host ? (size_t)(c->n_lib + 1) * 3 * (size_t)hist_len : 0, norg = hist_host ? (size_t)(c->n_lib + 1) : 0;
   const int n_split = (int)c->max_split + 1;
@@ -651,12 +651,12 @@ namespace elp {
 // call (they are taken back whatever happens: the shadow owns nothing but its scratch), runs on its own stream behind what the context's
 // stream holds now, and returns when its own stream is done - the context's stream never waits for it.
 static int metrics_on_side(elp_ctx *c, int dist, int64_t *counters_host, int64_t *hist_host, int hist_len) {
-  if (!c->marked) return set_error(c, ELP_ERR_ARG, "elp_dup_metrics: call elp_mark_duplicates first");
+  if (!c->derived.marked) return set_error(c, ELP_ERR_ARG, "elp_dup_metrics: call elp_mark_duplicates first");
   // (the time-out word of mark duplicates' radix passes is the context's: whoever reads its error words next - the sort's last read-back,
   // elp_sync, elp_get_flags - reports it; reading it here would wait for the context's whole stream)
   elp_ctx *s = nullptr;
   ELP_TRY(side_lane(c, 0, &s));
-  s->n = c->n; s->n_lib = c->n_lib; s->n_rg = c->n_rg; s->n_ref = c->n_ref; s->max_split = c->max_split; s->marked = c->marked;
+  s->n = c->n; s->n_lib = c->n_lib; s->n_rg = c->n_rg; s->n_ref = c->n_ref; s->max_split = c->max_split; s->derived.marked = c->derived.marked;
   s->n_sr = c->n_sr; s->n_filtered = c->n_filtered;
   s->flag.p = c->flag.p; s->rgid.p = c->rgid.p; s->rg_lib.p = c->rg_lib.p; s->refid.p = c->refid.p; s->qname_off.p = c->qname_off.p; s->qname.p = c->qname.p;
   s->pair_win.p = c->pair_win.p; s->mate.p = c->mate.p; s->has_sr.p = c->has_sr.p; s->upos.p = c->upos.p; s->split.p = c->split.p;

@@ -244,8 +244,7 @@ static int sort_queryname(elp_ctx *c) {
     return rc;
   }
   ELP_TRY(side_join(c, 1));
-  c->sorted = true;
-  c->sorted_qname = true;
+  c->derived.set_sorted(true);
   return 0;
 }
 
@@ -254,7 +253,6 @@ static int sort_queryname(elp_ctx *c) {
 extern "C" int elp_sort_queryname(elp_ctx *c) {
   if (!c) return ELP_ERR_ARG;
   ELP_HIP(c, hipSetDevice(c->device));
-  c->sorted = false;
-  c->sorted_qname = false;
+  c->derived.drop_sorted();
   return elp::sort_queryname(c);
 }

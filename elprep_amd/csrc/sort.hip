@@ -308,8 +308,8 @@ static int score_uniform_launch(elp_ctx *c) {
   ELP_LAUNCH(c, "adapt_score", k_score_uniform<R>, dim3(grid), dim3(64 * SU_WAVES), dyn, c->n, L, (const uint8_t *)c->qual.p, (const uint16_t *)c->flag.p,
              c->score.p, c->qbounds.p, c->adapt_err.p, qstride, reinterpret_cast<unsigned long long *>(c->adapt_err.p + 2), (const uint16_t *)c->rgid.p,
              (const uint16_t *)c->rg_cov.p, arecs);
-  c->adapt_sampled = true;
-  c->apply_recs_valid = arecs != nullptr;
+  c->derived.adapt_sampled = true;
+  c->derived.apply_recs_valid = arecs != nullptr;
   c->apply_recs_lmax = (int)L;
   return 0;
 }
@@ -376,14 +376,14 @@ __global__ __launch_bounds__(256) void k_flat_index(const uint64_t *__restrict__
 }
 
 int ensure_flat_index(elp_ctx *c) {
-  if (c->flat_index_n == c->n && c->flat_index_bytes == c->qual_bytes && c->n) return 0;
+  if (c->derived.has_flat_index(c->n, c->qual_bytes)) return 0;
   const uint64_t ntiles = (c->qual_bytes + FL_TILE - 1) / FL_TILE;
   ELP_TRY(ensure(c, c->tile_first, ntiles + 2));
   if (c->n)
     ELP_LAUNCH(c, "flat_index", k_flat_index, dim3(blocks_for(ntiles + 1, 256)), dim3(256), 0, (const uint64_t *)c->qual_off.p, c->n, ntiles,
                c->tile_first.p);
-  c->flat_index_n = c->n;
-  c->flat_index_bytes = c->qual_bytes;
+  c->derived.flat_index_n = c->n;
+  c->derived.flat_index_bytes = c->qual_bytes;
   return 0;
 }
 
@@ -398,10 +398,10 @@ __global__ __launch_bounds__(256) void k_uniform_check(uint64_t n, const uint64_
   if (__any(b) && (threadIdx.x & 63) == 0) atomicOr(bad, 1u);
 }
 int ensure_uniform_len(elp_ctx *c) {
-  if (c->uniform_n == c->n && c->uniform_bytes == c->qual_bytes && c->n) return 0;
+  if (c->derived.has_uniform(c->n, c->qual_bytes)) return 0;
   c->uniform_len = 0;
-  c->uniform_n = c->n;
-  c->uniform_bytes = c->qual_bytes;
+  c->derived.uniform_n = c->n;
+  c->derived.uniform_bytes = c->qual_bytes;
   if (!c->n || c->qual_bytes % c->n) return 0;
   const uint64_t len = c->qual_bytes / c->n;
   if (len == 0 || len > 0x3FFFFFull) return 0;
@@ -426,7 +426,7 @@ int adapt_quality_error(elp_ctx *c) {
 // the quality-error word of the score kernel, read when somebody needs it (check_quals) - or by elp_mark_duplicates together with its
 // own first read-back (adapt_note): the adapt stage has no synchronisation of its own
 static int adapt_resolve(elp_ctx *c) {
-  if (!c->adapt_pending) return 0;
+  if (!c->derived.adapt_pending) return 0;
   uint32_t w[ADAPT_WORDS];
   ELP_HIP(c, hipMemcpyAsync(w, c->adapt_err.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
   ELP_HIP(c, elp::stream_wait(c->stream));
@@ -435,12 +435,10 @@ static int adapt_resolve(elp_ctx *c) {
 }
 // words: [0] the score kernel's error word, [2 .. 5] the quality values its sampled groups saw (k_score_uniform only)
 void adapt_note(elp_ctx *c, const uint32_t *words) {
-  c->adapt_pending = false;
-  if (words[0] & 1u) c->adapt_bad_qual = true;
-  if (c->adapt_sampled) {
+  c->derived.adapt_word_read((words[0] & 1u) != 0);
+  if (c->derived.adapt_sampled) {
     c->adapt_qmask[0] = (unsigned long long)words[2] | ((unsigned long long)words[3] << 32);
     c->adapt_qmask[1] = (unsigned long long)words[4] | ((unsigned long long)words[5] << 32);
-    c->adapt_qmask_valid = true;
   }
 }
 int adapt_begin(elp_ctx *c, int *pos_bits_out) {
@@ -453,11 +451,7 @@ int adapt_begin(elp_ctx *c, int *pos_bits_out) {
   ELP_TRY(ensure(c, c->qbounds, n + 1));
   ELP_TRY(ensure(c, c->adapt_err, ADAPT_WORDS + 2));
   ELP_HIP(c, hipMemsetAsync(c->adapt_err.p, 0, ADAPT_WORDS * sizeof(uint32_t), c->stream));
-  c->adapt_bad_qual = false;
-  c->adapt_pending = false;
-  c->adapt_sampled = c->adapt_qmask_valid = false;
-  c->apply_recs_valid = false;
-  c->adapt_epoch++;  // (the key column is about to be rewritten: sorted words made from it are stale)
+  c->derived.adapt_begins();
   int pos_bits = 1;
   while (pos_bits < 32 && (c->max_pos >> pos_bits) != 0) pos_bits++;
   int ref_bits = 1;  // contig codes 0 .. n_ref + 1 (unmapped, then the records that are not sorted at all)
@@ -484,13 +478,13 @@ int adapt_scores(elp_ctx *c) {
     ELP_LAUNCH(c, "adapt_score_flat", k_score_flat, dim3(grid), dim3(FL_THREADS), 0, n, (const uint64_t *)c->qual_off.p, (const uint8_t *)c->qual.p,
                c->qual_bytes, (const uint32_t *)c->tile_first.p, (const uint16_t *)c->flag.p, c->score.p, c->qbounds.p, c->adapt_err.p);
   }
-  c->adapt_pending = true;
+  c->derived.adapt_pending = true;
   return 0;
 }
 int ensure_adapted(elp_ctx *c, bool check_quals) {
-  if (c->adapted) {
+  if (c->derived.adapted()) {
     if (check_quals) ELP_TRY(adapt_resolve(c));
-    return (check_quals && c->adapt_bad_qual) ? adapt_quality_error(c) : 0;
+    return (check_quals && c->derived.adapt_bad_qual) ? adapt_quality_error(c) : 0;
   }
   int pos_bits = 1;
   ELP_TRY(adapt_begin(c, &pos_bits));
@@ -501,17 +495,19 @@ int ensure_adapted(elp_ctx *c, bool check_quals) {
                (uint32_t)c->n_ref, pos_bits, (const uint8_t *)c->has_sr.p);
     ELP_TRY(adapt_scores(c));
   }
-  c->adapted = true;
+  c->derived.keys = c->derived.scores = true;
   if (check_quals) ELP_TRY(adapt_resolve(c));
-  return (check_quals && c->adapt_bad_qual) ? adapt_quality_error(c) : 0;
+  return (check_quals && c->derived.adapt_bad_qual) ? adapt_quality_error(c) : 0;
 }
+// all the coordinate sort asks for: it reads no score, so nothing elp_bqsr_apply spoils sends it back into the adapt stage
+int ensure_keys(elp_ctx *c) { return c->derived.keys ? 0 : ensure_adapted(c, false); }
 
 // c->qual_present = quality values seen in a sample of the QUAL column (a sizing hint, see k_qual_present_sample)
 int ensure_qual_present(elp_ctx *c, bool exact) {
-  if (c->have_qual_present) return 0;
+  if (c->derived.have_qual_present) return 0;
   c->qual_present[0] = c->qual_present[1] = 0;
   // elp_set_tuning "qual_hint" = 1: the hint stays empty, which forces the gather's report-and-retry path (tests)
-  if (!exact && c->tune.qual_hint != 1 && c->adapted && c->adapt_sampled) {
+  if (!exact && c->tune.qual_hint != 1 && c->derived.scores && c->derived.adapt_sampled) {
     // the score kernel sampled the column as it went (k_score_uniform): no pass, and no wait of its own if the error word is in already
     ELP_TRY(adapt_resolve(c));
     c->qual_present[0] = c->adapt_qmask[0];
@@ -534,7 +530,7 @@ int ensure_qual_present(elp_ctx *c, bool exact) {
     if (q < 64) c->qual_present[0] &= ~(1ull << q);
     else if (q < 128) c->qual_present[1] &= ~(1ull << (q - 64));
   }
-  c->have_qual_present = true;
+  c->derived.have_qual_present = true;
   return 0;
 }
 
@@ -896,9 +892,9 @@ __global__ __launch_bounds__(256) void k_large_scatter(uint32_t nu, const uint32
 
 static int sort_impl(elp_ctx *c, uint64_t *presorted = nullptr /* the key passes' result, made ahead (sort_presort) */) {
   const uint64_t n = c->n;
-  ELP_TRY(ensure_adapted(c, false));
+  ELP_TRY(ensure_keys(c));
   ELP_TRY(ensure(c, c->perm, n + 1));
-  if (n == 0) { c->sorted = true; return 0; }
+  if (n == 0) { c->derived.set_sorted(false); return 0; }
   uint64_t *kbuf;
   uint32_t *vbuf, *flags;
   ELP_TRY(scratch(c, 0, 2 * n + 8, &kbuf));
@@ -1076,7 +1072,7 @@ static int sort_impl(elp_ctx *c, uint64_t *presorted = nullptr /* the key passes
         }
         if (settled) {
           c->radix_check_pending = true;
-          c->sorted = true;
+          c->derived.set_sorted(false);
           return 0;
         }
       }
@@ -1130,7 +1126,7 @@ static int sort_impl(elp_ctx *c, uint64_t *presorted = nullptr /* the key passes
   // (a look-back that timed out leaves a wrong permutation: the bit is read by whoever reads the error words next - the following
   // stage, elp_sync, elp_get_permutation, the emit calls: fetch_err - instead of a synchronisation of its own here)
   c->radix_check_pending = true;
-  c->sorted = true;
+  c->derived.set_sorted(false);
   return 0;
 }
 
@@ -1141,20 +1137,22 @@ namespace elp {
 // permutation's buffer as views for the duration of the call, runs on its own stream behind what the context's stream holds now, and
 // before it returns the context's stream is made to wait for whatever the lane still has queued - later stages find the permutation.
 static int sort_on_side(elp_ctx *c) {
-  ELP_TRY(ensure_adapted(c, false));  // (on the context: the shadow takes the key column as it is)
+  ELP_TRY(ensure_keys(c));  // (on the context: the shadow takes the key column as it is)
   ELP_TRY(ensure(c, c->perm, c->n + 1));
   elp_ctx *s = nullptr;
   ELP_TRY(side_lane(c, 1, &s));
   s->n = c->n; s->n_sr = c->n_sr; s->n_filtered = c->n_filtered; s->key_bits = c->key_bits; s->max_qname_len = c->max_qname_len; s->max_pos = c->max_pos;
-  s->n_ref = c->n_ref; s->adapted = true; s->adapt_pending = false; s->sorted = false;
+  s->n_ref = c->n_ref;
+  s->derived = elp::Derived{};
+  s->derived.keys = true;  // (of what the context has derived the shadow sees the key column, nothing else)
   s->key.p = c->key.p; s->flag.p = c->flag.p; s->mapq.p = c->mapq.p; s->next_refid.p = c->next_refid.p; s->pnext.p = c->pnext.p; s->tlen.p = c->tlen.p;
   s->qname_off.p = c->qname_off.p; s->qname.p = c->qname.p; s->has_sr.p = c->has_sr.p;
   s->perm.p = c->perm.p; s->perm.cap = c->perm.cap;
   // the key passes may have been queued ahead (elp_sort_ahead, from inside elp_mark_duplicates): same keys, same length, same lane
   int ib = 1;
   while (ib < 32 && (c->n >> ib) != 0) ib++;
-  uint64_t *pre = (c->presort_ks && c->presort_epoch == c->adapt_epoch && c->presort_n == c->n && c->presort_idx_bits == ib && c->tune.sort_pairs != 1) ? c->presort_ks : nullptr;
-  c->presort_epoch = ~0ull;  // (used once: the tie-break leaves its marks in the buffer's other half)
+  uint64_t *pre = (c->presort_ks && c->derived.presorted && c->presort_n == c->n && c->presort_idx_bits == ib && c->tune.sort_pairs != 1) ? c->presort_ks : nullptr;
+  c->derived.drop_presort();  // (used once: the tie-break leaves its marks in the buffer's other half)
   int rc = sort_impl(s, pre);
   s->key.p = nullptr; s->flag.p = nullptr; s->mapq.p = nullptr; s->next_refid.p = nullptr; s->pnext.p = nullptr; s->tlen.p = nullptr;
   s->qname_off.p = nullptr; s->qname.p = nullptr; s->has_sr.p = nullptr;
@@ -1166,7 +1164,7 @@ static int sort_on_side(elp_ctx *c) {
     return rc;
   }
   ELP_TRY(side_join(c, 1));
-  c->sorted = s->sorted;
+  c->derived.set_sorted(false);
   return 0;
 }
 }  // namespace elp
@@ -1174,8 +1172,8 @@ static int sort_on_side(elp_ctx *c) {
 namespace elp {
 int sort_presort(elp_ctx *c) {
   const uint64_t n = c->n;
-  c->presort_epoch = ~0ull;
-  if (!c->sort_ahead || n < 2 || !c->adapted || c->tune.sort_pairs == 1) return 0;
+  c->derived.drop_presort();
+  if (!c->sort_ahead || n < 2 || !c->derived.keys || c->tune.sort_pairs == 1) return 0;
   int idx_bits = 1;
   while (idx_bits < 32 && (n >> idx_bits) != 0) idx_bits++;
   if (c->key_bits < 1 || c->key_bits + idx_bits > 64) return 0;  // (pairs, not words: the sort makes its passes itself)
@@ -1189,7 +1187,7 @@ int sort_presort(elp_ctx *c) {
   if (rc == 0) rc = radix_sort_fused(s, c->key.p, n, c->key_bits, idx_bits, kbuf, kbuf + n, &ks);
   s->tune.radix_tile = tile_saved;
   if (rc != 0) { c->err = s->err; return rc; }
-  c->presort_ks = ks; c->presort_n = n; c->presort_idx_bits = idx_bits; c->presort_epoch = c->adapt_epoch;
+  c->presort_ks = ks; c->presort_n = n; c->presort_idx_bits = idx_bits; c->derived.presorted = true;
   return 0;
 }
 }  // namespace elp
@@ -1197,13 +1195,13 @@ int sort_presort(elp_ctx *c) {
 extern "C" int elp_sort_ahead(elp_ctx *c, int on) {
   if (!c) return ELP_ERR_ARG;
   c->sort_ahead = on != 0;
-  if (!on) c->presort_epoch = ~0ull;
+  if (!on) c->derived.drop_presort();
   return 0;
 }
 
 extern "C" int elp_sort_coordinate(elp_ctx *c) {
   if (!c) return ELP_ERR_ARG;
   ELP_HIP(c, hipSetDevice(c->device));
-  c->sorted = c->sorted_qname = false;
+  c->derived.drop_sorted();
   return elp::sort_on_side(c);
 }

@@ -219,7 +219,11 @@ int elp_merge_spread(elp_ctx *groups, elp_ctx *spread, uint64_t *slot_of_spread_
  * on the same context: the three chains need nothing of each other (the reference runs them one after the other,
  * cmd/filter.go:162-196).  The call returns when the permutation is complete; calls that read it afterwards (elp_get_permutation,
  * elp_emit_*) are ordered behind it.  Calls that CHANGE staged records (staging, reset, rollback, filters, exchange) must not overlap
- * with any other call on the context. */
+ * with any other call on the context.  What the sort's thread touches of the context: it READS the key column with its validity item
+ * "keys" (csrc/derived.hpp - elp_mark_duplicates leaves it valid and no BQSR call clears it: elp_bqsr_apply spoils the scores and the
+ * quality hint only, so the sort never enters the adapt stage nor the context's own stream), the comparator's columns (QNAME, FLAG,
+ * MAPQ, RNEXT, PNEXT, TLEN) and the record-state column; it WRITES the permutation, its items "sorted" / "sorted_qname", and the
+ * bookkeeping of key passes made ahead (elp_sort_ahead). */
 int elp_sort_coordinate(elp_ctx *ctx);
 /* on != 0: the host announces that elp_sort_coordinate will follow elp_mark_duplicates on this context (what `elprep filter
  * --mark-duplicates --sorting-order coordinate` does, sam/filter-pipeline.go:116).  The sort's key passes read the coordinate keys only -
@@ -245,7 +249,9 @@ int elp_get_permutation(elp_ctx *ctx, uint32_t *perm_out /* n */);
  * Concurrency: as elp_sort_coordinate - the sort runs on the same side lane of the context (a stream, scratch pool and error words of
  * its own) and writes the permutation only; once elp_mark_duplicates has returned, a host may call it from a thread of its own WHILE
  * other threads call elp_dup_metrics and drive elp_bqsr_gather(_device) -> finalize -> elp_bqsr_apply on the same context.  Calls that
- * CHANGE staged records must not overlap with it.  Limits as for staging: 2^32-16 records, QNAMEs of at most 1000 bytes. */
+ * CHANGE staged records must not overlap with it.  Its thread READS the QNAME and record-state columns and WRITES the permutation and its
+ * validity items "sorted" / "sorted_qname" (csrc/derived.hpp), nothing else of the context.  Limits as for staging: 2^32-16 records,
+ * QNAMEs of at most 1000 bytes. */
 int elp_sort_queryname(elp_ctx *ctx);
 /* number of records that survive RemoveOptionalReads = staged records without the sr tag: the first elp_num_sorted() entries of
  * the permutation are the output of the run, the tagged copies follow behind them */
