@@ -15,6 +15,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # ELP_HIP_SO: another build of the same library (A/B timing of two builds on one box, tools/prof/path_ab.py); never a fallback
 HIP_SO = os.environ.get("ELP_HIP_SO") or os.path.join(_PKG, "libelprep_hip.so")
 HOST_SO = os.path.join(_PKG, "libelprep_host.so")
+ELP_AB_BUILD = bool(os.environ.get("ELP_HIP_SO"))
 
 _hip: Optional[C.CDLL] = None
 _host: Optional[C.CDLL] = None
@@ -25,7 +26,7 @@ HIP_SYMBOLS = [
     "elp_dup_metrics", "elp_dup_metrics_hist", "elp_bqsr_set_reference", "elp_bqsr_set_known_sites", "elp_bqsr_gather", "elp_bqsr_apply", "elp_get_qual",
     "elp_bqsr_gather_device", "elp_bqsr_tables_fetch", "elp_bqsr_quals_counted", "elp_bqsr_tables_fetch_rows", "elp_bqsr_lut_upload_rows", "elp_group_unique_id", "elp_group_init", "elp_group_rank", "elp_group_size",
     "elp_bqsr_tables_add", "elp_bqsr_tables_allreduce", "elp_allreduce_i64",
-    "elp_filter_records", "elp_clean_sam", "elp_split_classify", "elp_merge_spread",
+    "elp_filter_records", "elp_clean_sam", "elp_set_tag_filter", "elp_set_replace_read_group", "elp_filter_exact_strict", "elp_clear_duplicate_flag", "elp_split_classify", "elp_merge_spread",
     "elp_set_read_group_ids", "elp_pinned_alloc", "elp_pinned_free", "elp_stage_bam", "elp_emit_sorted_bam", "elp_stage_bgzf", "elp_emit_sorted_bgzf",
     "elp_set_header_columns", "elp_stage_columns", "elp_set_read_group_ids_flat", "elp_filter_records_flat", "elp_group_probe", "elp_group_init_transport", "elp_copy_records", "elp_exchange_records", "elp_group_set_p2p", "elp_group_share", "elp_emit_merged_bam", "elp_bqsr_lut_upload",
     "elp_snapshot", "elp_rollback", "elp_set_tuning", "elp_profile_enable", "elp_profile_reset", "elp_profile_count", "elp_profile_get", "elp_debug_check_guards",
@@ -94,6 +95,13 @@ def hip() -> C.CDLL:
         L.elp_stage_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint16]
         L.elp_filter_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.elp_clean_sam.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        # (an older build named by ELP_HIP_SO for A/B timing lacks these four; calling one of them there still fails, with AttributeError)
+        for name, args in (("elp_set_tag_filter", [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+                           ("elp_set_replace_read_group", [C.c_void_p, C.c_char_p, C.c_int]),
+                           ("elp_filter_exact_strict", [C.c_void_p, C.POINTER(C.c_uint64)]), ("elp_clear_duplicate_flag", [C.c_void_p])):
+            if ELP_AB_BUILD and not hasattr(L, name):
+                continue
+            getattr(L, name).argtypes = args
         L.elp_split_classify.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.elp_merge_spread.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.elp_bqsr_gather_device.argtypes = [C.c_void_p, C.c_int]

@@ -15,61 +15,9 @@
 #include <thread>
 
 #include "common.hpp"
+#include "bamtag.hpp"
 
 namespace elp {
-
-__device__ __forceinline__ uint32_t ld_u16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-__device__ __forceinline__ void st_u16(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); }
-__device__ __forceinline__ void st_u32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
-
-// bytes of the value of one optional field of type `t` at p (end = end of the record); 0 = malformed
-__device__ inline uint32_t tag_value_size(uint8_t t, const uint8_t *p, const uint8_t *end) {
-  switch (t) {
-    case 'A': case 'c': case 'C': return 1;
-    case 's': case 'S': return 2;
-    case 'i': case 'I': case 'f': return 4;
-    case 'Z': case 'H': {
-      uint32_t k = 0;
-      while (p + k < end && p[k] != 0) k++;
-      return p + k < end ? k + 1 : 0;
-    }
-    case 'B': {
-      if (p + 5 > end) return 0;
-      const uint8_t st = p[0];
-      const uint32_t cnt = ld_u32(p + 1);
-      const uint32_t es = (st == 'c' || st == 'C') ? 1 : ((st == 's' || st == 'S') ? 2 : ((st == 'i' || st == 'I' || st == 'f') ? 4 : 0));
-      if (!es) return 0;
-      const uint64_t sz = 5ull + (uint64_t)cnt * es;  // 64-bit: a malformed count must not wrap into a small size
-      return sz > (uint64_t)(end - p) ? 0u : (uint32_t)sz;
-    }
-    default: return 0;
-  }
-}
-__device__ __forceinline__ bool tag_is_int(uint8_t t) { return t == 'c' || t == 'C' || t == 's' || t == 'S' || t == 'i' || t == 'I'; }
-__device__ inline long long tag_int_value(uint8_t t, const uint8_t *p) {
-  switch (t) {
-    case 'c': return (long long)(int8_t)p[0];
-    case 'C': return (long long)p[0];
-    case 's': return (long long)(int16_t)ld_u16(p);
-    case 'S': return (long long)ld_u16(p);
-    case 'i': return (long long)(int32_t)ld_u32(p);
-    default: return (long long)ld_u32(p);
-  }
-}
-// formatBamTag's integer rule (:492-525): type and size of the re-encoded value
-__device__ inline uint32_t int_out(long long v, uint8_t *type) {
-  if (v < 0) {
-    if (v >= -128) { *type = 'c'; return 1; }
-    if (v >= -32768) { *type = 's'; return 2; }
-    *type = 'i';
-    return 4;
-  }
-  if (v <= 255) { *type = 'C'; return 1; }
-  if (v <= 65535) { *type = 'S'; return 2; }
-  *type = 'I';
-  return 4;
-}
 
 struct BamIn {
   const uint8_t *raw;        // records of this piece (device copy); rec_off are offsets from raw
@@ -84,6 +32,7 @@ struct BamIn {
   const uint8_t *rg_ids;     // header read-group ids, concatenated
   const uint32_t *rg_off;    // n_rg + 1
   int32_t n_rg, n_ref;
+  int32_t replace_rg;        // elp_set_replace_read_group: every record is of read group 0, RG fields are not looked up
   uint16_t split_id;
   uint32_t *stats;           // [0] max QNAME length, [1] max l_seq, [2] max POS, [3] sr-tagged records, [4] error bits
 };
@@ -117,7 +66,7 @@ __global__ __launch_bounds__(256) void k_bam_fixed(BamIn m) {
     m.len_s[r] = err ? 0 : seqb;
     m.len_l[r] = err ? 0 : l_seq;
     // optional fields: RG:Z -> dense id of the header's read groups, sr -> record state (:373-396)
-    uint32_t rg = ELP_NIL16;
+    uint32_t rg = m.replace_rg ? 0u : ELP_NIL16;  // (aln.SetRG(id) runs on every alignment, with or without an RG field)
     if (!err) {
       const uint8_t *t = rec + fixed;
       while (t + 3 <= end) {
@@ -127,7 +76,7 @@ __global__ __launch_bounds__(256) void k_bam_fixed(BamIn m) {
         if (!sz || v + sz > end) { err |= 2u; break; }
         if (k0 == 's' && k1 == 'r') sr = true;
         if (k0 == 'C' && k1 == 'G' && ty == 'B') err |= 4u;  // CIGAR in a tag (> 65535 operations): not supported
-        if (k0 == 'R' && k1 == 'G' && ty == 'Z') {
+        if (k0 == 'R' && k1 == 'G' && ty == 'Z' && !m.replace_rg) {
           const uint32_t l = sz - 1;
           rg = 0xFFFEu;  // a read group the header does not know
           for (int g = 0; g < m.n_rg; g++) {
@@ -203,8 +152,17 @@ struct BamOut {
   const uint64_t *qname_off, *cigar_off, *qual_off;
   const uint8_t *qname, *qual;
   const uint32_t *cigar;
+  const uint32_t *drop;      // elp_set_tag_filter: bit k = fields with the 16-bit key k stay behind (65536 bits); nullptr = no filter
+  const uint8_t *rg_new;     // elp_set_replace_read_group: the id every record goes out with (rg_on), rg_len bytes
+  uint32_t rg_len, rg_on;
 };
+constexpr uint32_t KEY_RG = tag_key_of('R', 'G');
+// filters2's RemoveOptionalFields / KeepOptionalFields (filters/simple-filters.go:235-288) as one look-up: every field of a key goes or stays
+__device__ __forceinline__ bool tag_dropped(const uint32_t *__restrict__ drop, uint32_t key) { return drop && ((drop[key >> 5] >> (key & 31)) & 1u); }
 // size of output record k (block_size field included); *tags_at = offset of the tags inside the input record
+// OPT: a tag filter or a replacing read group is set.  The walks are bound by their chain of dependent loads and the per-field tests cost
+// the emitter 8 % where nothing is set (measured), so a context without either runs the instantiation without them.
+template <bool OPT>
 __device__ inline uint32_t out_size(const BamOut &m, uint32_t i, uint32_t *err) {
   const uint8_t *p = m.raw + m.raw_off[i];
   const uint32_t bs = ld_u32(p);
@@ -215,16 +173,29 @@ __device__ inline uint32_t out_size(const BamOut &m, uint32_t i, uint32_t *err) 
   const uint64_t n_cig_out = m.cigar_off[i + 1] - m.cigar_off[i];
   uint32_t size = 4 + (uint32_t)(fixed + 4ull * n_cig_out - 4ull * n_cig);
   const uint8_t *t = rec + fixed;
+  bool rg_seen = false;
   while (t + 3 <= end) {
     const uint8_t ty = t[2];
     const uint8_t *v = t + 3;
     const uint32_t sz = tag_value_size(ty, v, end);
     if (!sz) { *err |= 2u; break; }
     if (ty == 'H') *err |= 16u;  // parseBamByteArray looks for the character '0' as the terminator (:203): not reproduced
+    // (both errors also for a field the filter drops: the reference parses a record before it filters it)
     uint8_t ot;
-    size += 3 + (tag_is_int(ty) ? int_out(tag_int_value(ty, v), &ot) : sz);
+    if constexpr (OPT) {
+      const uint32_t key = tag_key(t);
+      if (!tag_dropped(m.drop, key)) {
+        if (m.rg_on && key == KEY_RG && !rg_seen) size += 4 + m.rg_len;  // SmallMap.Set (utils/small-map.go:59-67): the FIRST field of the key, whatever its type
+        else size += 3 + (tag_is_int(ty) ? int_out(tag_int_value(ty, v), &ot) : sz);
+      }
+      rg_seen |= key == KEY_RG;
+    } else {
+      size += 3 + (tag_is_int(ty) ? int_out(tag_int_value(ty, v), &ot) : sz);
+    }
     t = v + sz;
   }
+  if constexpr (OPT)
+    if (m.rg_on && !rg_seen && !tag_dropped(m.drop, KEY_RG)) size += 4 + m.rg_len;  // ... else appended behind the last field
   return size;
 }
 // Output record k of a MERGED stream (elp_emit_merged_bam) comes from one of two contexts: src[k] = rank of the record in the first
@@ -237,13 +208,14 @@ __device__ __forceinline__ const BamOut &out_source(const BamOut &m, const BamOu
   *i = mm.perm[s & ~MERGE_SECOND];
   return mm;
 }
+template <bool OPT>
 __global__ __launch_bounds__(256) void k_bam_out_sizes(BamOut m, BamOut m2, const uint32_t *__restrict__ src, uint64_t k0, uint32_t cnt, uint32_t *__restrict__ sizes,
                                                        uint32_t *err) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= cnt) return;
   uint32_t e = 0, i;
   const BamOut &mm = out_source(m, m2, src, k0 + j, &i);
-  sizes[j] = out_size(mm, i, &e);
+  sizes[j] = out_size<OPT>(mm, i, &e);
   if (e) atomicOr(err, e);
 }
 // Alignment.bin(), sam/bam-files.go:443-468
@@ -256,6 +228,7 @@ __device__ inline uint32_t reg2bin(int32_t beg, int32_t end) {
   return 0;
 }
 // one wavefront per output record; `out` = this chunk's buffer, offs = exclusive scan of the chunk's sizes
+template <bool OPT>
 __global__ __launch_bounds__(256) void k_bam_out_emit(BamOut m_first, BamOut m_second, const uint32_t *__restrict__ src, uint64_t k0, uint32_t cnt,
                                                       const uint32_t *__restrict__ offs, uint8_t *__restrict__ out) {
   const uint32_t lane = threadIdx.x & 63;
@@ -300,6 +273,9 @@ __global__ __launch_bounds__(256) void k_bam_out_emit(BamOut m_first, BamOut m_s
       // that stays as it is is copied by all lanes; only an integer's new form is written by lane 0.
       uint8_t *w = o + 4 + fixed;
       const uint8_t *t = rec + (32ull + l_name + 4ull * ld_u16(rec + 12) + ((ld_u32(rec + 16) + 1) >> 1) + ld_u32(rec + 16));
+      // elp_set_tag_filter / elp_set_replace_read_group: the same walk - a dropped field is skipped by the whole wave together (the key
+      // and the table's word are wave-uniform), the first RG field goes out as RG:Z:<id>, a record without one gets it behind its last field
+      bool rg_seen = false;
       while (t + 3 <= end) {
         const uint8_t ty = t[2];
         const uint8_t *v = t + 3;
@@ -317,7 +293,19 @@ __global__ __launch_bounds__(256) void k_bam_out_emit(BamOut m_first, BamOut m_s
           sz = tag_value_size(ty, v, end);
         }
         if (!sz) break;
-        if (tag_is_int(ty)) {
+        bool dropped = false, is_rg = false;
+        if constexpr (OPT) {
+          const uint32_t key = tag_key(t);
+          dropped = tag_dropped(m.drop, key);
+          is_rg = m.rg_on && key == KEY_RG && !rg_seen;
+          rg_seen |= key == KEY_RG;
+        }
+        if (dropped) {
+        } else if (is_rg) {
+          if (lane == 0) { w[0] = 'R'; w[1] = 'G'; w[2] = 'Z'; w[3 + m.rg_len] = 0; }
+          for (uint32_t b = lane; b < m.rg_len; b += 64) w[3 + b] = m.rg_new[b];
+          w += 4 + m.rg_len;
+        } else if (tag_is_int(ty)) {
           const long long val = tag_int_value(ty, v);
           uint8_t ot;
           const uint32_t os = int_out(val, &ot);
@@ -331,6 +319,11 @@ __global__ __launch_bounds__(256) void k_bam_out_emit(BamOut m_first, BamOut m_s
           w += 3 + sz;
         }
         t = v + sz;
+      }
+      if (OPT && m.rg_on && !rg_seen && !tag_dropped(m.drop, KEY_RG)) {
+        if (lane == 0) { w[0] = 'R'; w[1] = 'G'; w[2] = 'Z'; w[3 + m.rg_len] = 0; }
+        for (uint32_t b = lane; b < m.rg_len; b += 64) w[3 + b] = m.rg_new[b];
+        w += 4 + m.rg_len;
       }
       if (lane == 0) st_u32(o, (uint32_t)(w - o - 4));  // block_size
     }
@@ -365,7 +358,7 @@ int stage_bam_columns(elp_ctx *c, uint32_t n_rec, uint64_t piece_bytes, uint64_t
            *sc_l = wk + 7 * np, *stats = wk + 8 * np;
   ELP_HIP(c, hipMemsetAsync(stats, 0, 32, st));
   BamIn in{c->raw.p, c->raw_off.p + c->n, n_rec, c->n, c->refid.p, c->pos.p, c->next_refid.p, c->pnext.p, c->tlen.p, c->flag.p, c->rgid.p, c->split.p,
-           c->mapq.p, c->has_sr.p, c->l_seq.p, len_q, len_c, len_s, len_l, c->rg_ids.p, c->rg_ids_off.p, c->n_rg, c->n_ref, split_id, stats};
+           c->mapq.p, c->has_sr.p, c->l_seq.p, len_q, len_c, len_s, len_l, c->rg_ids.p, c->rg_ids_off.p, c->n_rg, c->n_ref, c->replace_rg ? 1 : 0, split_id, stats};
   ELP_LAUNCH(c, "stage_bam_fixed", k_bam_fixed, dim3(blocks_for(n_rec, 256)), dim3(256), 0, in);
   uint32_t tq = 0, tc = 0, ts = 0, tl = 0;
   ELP_TRY(exclusive_scan_u32(c, len_q, sc_q, n_rec, &tq));
@@ -438,6 +431,53 @@ int elp_set_read_group_ids_flat(elp_ctx *c, const uint8_t *ids, const uint32_t *
   return elp_set_read_group_ids(c, ptr.data());
 }
 
+// RemoveOptionalFields / KeepOptionalFields (filters/simple-filters.go:235-288) in filters2's order - remove, then keep
+// (cmd/filter.go:878-902) - folded into ONE table of 65536 bits on the host: bit k set = a field whose two key bytes read as the number
+// k does not go out.  SmallMap.DeleteIf drops every entry that matches (utils/small-map.go:89-99), so the key alone decides.
+int elp_set_tag_filter(elp_ctx *c, const uint8_t *remove_keys, int n_remove, const uint8_t *keep_keys, int n_keep) {
+  if (!c) return ELP_ERR_ARG;
+  if (n_remove < -1 || n_keep < -1 || (n_remove > 0 && !remove_keys) || (n_keep > 0 && !keep_keys)) return set_error(c, ELP_ERR_ARG, "elp_set_tag_filter: bad arguments");
+  if (n_remove > 4096 || n_keep > 4096) return set_error(c, ELP_ERR_UNSUPPORTED, "elp_set_tag_filter: more than 4096 keys in a list");
+  if (n_remove == 0 && n_keep == -1) { c->tag_filter = false; return 0; }
+  ELP_HIP(c, hipSetDevice(c->device));
+  std::vector<uint32_t> drop(elp_ctx::TAG_WORDS, n_remove == -1 ? 0xFFFFFFFFu : 0u);
+  for (int k = 0; k < n_remove; k++) {
+    const uint32_t key = (uint32_t)remove_keys[2 * k] | ((uint32_t)remove_keys[2 * k + 1] << 8);
+    drop[key >> 5] |= 1u << (key & 31);
+  }
+  if (n_keep >= 0) {
+    std::vector<uint32_t> keep(elp_ctx::TAG_WORDS, 0u);
+    for (int k = 0; k < n_keep; k++) {
+      const uint32_t key = (uint32_t)keep_keys[2 * k] | ((uint32_t)keep_keys[2 * k + 1] << 8);
+      keep[key >> 5] |= 1u << (key & 31);
+    }
+    for (size_t w = 0; w < drop.size(); w++) drop[w] |= ~keep[w];
+  }
+  ELP_TRY(ensure(c, c->tag_drop, elp_ctx::TAG_WORDS));
+  ELP_HIP(c, hipMemcpyAsync(c->tag_drop.p, drop.data(), drop.size() * 4, hipMemcpyHostToDevice, c->stream));
+  ELP_HIP(c, elp::stream_wait(c->stream));
+  c->h_tag_drop.swap(drop);
+  c->tag_filter = true;
+  return 0;
+}
+
+// AddOrReplaceReadGroup (filters/simple-filters.go:156-162): header.RG = []{readGroup}, aln.SetRG(id) on every alignment
+int elp_set_replace_read_group(elp_ctx *c, const uint8_t *id, int id_len) {
+  if (!c) return ELP_ERR_ARG;
+  if (id_len < 0 || id_len > 255 || (id_len && !id) || (id_len && memchr(id, 0, (size_t)id_len)))
+    return set_error(c, ELP_ERR_ARG, "elp_set_replace_read_group: the id must be 0 .. 255 bytes without a NUL");
+  std::lock_guard<std::mutex> g(c->stage_mu);
+  if (!c->have_header || c->n_rg != 1) return set_error(c, ELP_ERR_ARG, "elp_set_replace_read_group: call elp_set_header with a header of ONE read group (the new one) first");
+  if (c->n) return set_error(c, ELP_ERR_ARG, "elp_set_replace_read_group: records are staged already (the read group decides their library and covariate)");
+  ELP_HIP(c, hipSetDevice(c->device));
+  ELP_TRY(ensure(c, c->replace_rg_dev, 256));
+  if (id_len) ELP_HIP(c, hipMemcpyAsync(c->replace_rg_dev.p, id, (size_t)id_len, hipMemcpyHostToDevice, c->stream));
+  ELP_HIP(c, elp::stream_wait(c->stream));
+  c->replace_rg_id.assign(reinterpret_cast<const char *>(id), (size_t)id_len);
+  c->replace_rg = true;
+  return 0;
+}
+
 void *elp_pinned_alloc(size_t bytes) {
   void *p = nullptr;
   if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
@@ -454,7 +494,7 @@ int elp_stage_bam(elp_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint
   std::lock_guard<std::mutex> g(c->stage_mu);
   ELP_HIP(c, hipSetDevice(c->device));
   if (!c->have_header) return set_error(c, ELP_ERR_ARG, "elp_stage_bam: call elp_set_header first");
-  if (c->n_rg && !c->have_rg_ids) return set_error(c, ELP_ERR_ARG, "elp_stage_bam: call elp_set_read_group_ids first");
+  if (c->n_rg && !c->have_rg_ids && !c->replace_rg) return set_error(c, ELP_ERR_ARG, "elp_stage_bam: call elp_set_read_group_ids first");
   if (c->n != c->raw_n) return set_error(c, ELP_ERR_ARG, "elp_stage_bam: the context already holds records staged with elp_stage");
   hipStream_t st = c->stream;
   // pieces are committed one at a time: whatever was derived from the records staged so far is invalid from here on, also if a later
@@ -538,8 +578,9 @@ static int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint
                        uint64_t *n_bytes_out, bool bgzf = false) {
   // records per device pass: sizes and offsets of a pass are scanned in 32 bits, so a pass must stay below 4 GiB of output.  An output
   // record is never longer than the staged one (integer fields only shrink when re-encoded) - except that elp_clean_sam may have added
-  // ONE CIGAR operation (4 bytes) - so the largest staged record + 4 bounds it; BGZF framing adds 26 bytes per 65280 (< 0.1 %: the bound
-  // leaves 1/64 of headroom).
+  // ONE CIGAR operation (4 bytes), and elp_set_replace_read_group may have made the record's RG field longer or added one (RG:Z:<id> =
+  // 4 + id_len bytes; the caller adds that to max_raw_rec) - so the largest staged record + 4 (+ 4 + id_len) bounds it; BGZF framing adds
+  // 26 bytes per 65280 (< 0.1 %: the bound leaves 1/64 of headroom).  A tag filter only takes bytes away.
   uint32_t CHUNK = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1u << 21, 0xFC000000ull / (std::max<uint64_t>(max_raw_rec, 64) + 4)));
   if (c->tune.emit_pass > 0) CHUNK = std::min<uint32_t>(CHUNK, (uint32_t)c->tune.emit_pass);  // (elp_set_tuning: tests)
   uint64_t total = 0;
@@ -554,7 +595,9 @@ static int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint
     ELP_TRY(scratch(c, 4, (size_t)2 * (cnt + 8) + 8, &sizes));
     uint32_t *offs = sizes + cnt + 8, *err = offs + cnt + 8;
     ELP_HIP(c, hipMemsetAsync(err, 0, 4, st));
-    ELP_LAUNCH(c, "emit_bam_sizes", k_bam_out_sizes, dim3(blocks_for(cnt, 256)), dim3(256), 0, m, m2, src, k0, cnt, sizes, err);
+    const bool opt = m.drop != nullptr || m.rg_on;  // (m2 shares m's settings: elp_emit_merged_bam checks)
+    if (opt) ELP_LAUNCH(c, "emit_bam_sizes", k_bam_out_sizes<true>, dim3(blocks_for(cnt, 256)), dim3(256), 0, m, m2, src, k0, cnt, sizes, err);
+    else ELP_LAUNCH(c, "emit_bam_sizes", k_bam_out_sizes<false>, dim3(blocks_for(cnt, 256)), dim3(256), 0, m, m2, src, k0, cnt, sizes, err);
     uint32_t chunk_bytes = 0;
     ELP_TRY(exclusive_scan_u32(c, sizes, offs, cnt, &chunk_bytes));
     uint32_t he = 0;
@@ -574,7 +617,8 @@ static int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint
     ELP_TRY(scratch(c, 5, (size_t)pass_bytes + 64, &d_out));
     if (held) ELP_HIP(c, hipMemcpyAsync(d_out, carry.data(), held, hipMemcpyHostToDevice, st));
     const unsigned grid = std::min<unsigned>(blocks_for((uint64_t)cnt * 64, 256), (unsigned)c->n_cu * 32);
-    ELP_LAUNCH(c, "emit_bam", k_bam_out_emit, dim3(grid), dim3(256), 0, m, m2, src, k0, cnt, (const uint32_t *)offs, d_out + held);
+    if (opt) ELP_LAUNCH(c, "emit_bam", k_bam_out_emit<true>, dim3(grid), dim3(256), 0, m, m2, src, k0, cnt, (const uint32_t *)offs, d_out + held);
+    else ELP_LAUNCH(c, "emit_bam", k_bam_out_emit<false>, dim3(grid), dim3(256), 0, m, m2, src, k0, cnt, (const uint32_t *)offs, d_out + held);
     const uint8_t *d_send = d_out;
     if (bgzf) {
       uint8_t *d_framed = nullptr;
@@ -597,8 +641,11 @@ static int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint
 }
 static BamOut bam_out_of(const elp_ctx *c) {
   return BamOut{c->n - c->n_sr, c->perm.p, c->raw.p, c->raw_off.p, c->refid.p, c->pos.p, c->next_refid.p, c->pnext.p, c->tlen.p, c->flag.p, c->mapq.p, c->l_seq.p,
-                c->qname_off.p, c->cigar_off.p, c->qual_off.p, c->qname.p, c->qual.p, c->cigar.p};
+                c->qname_off.p, c->cigar_off.p, c->qual_off.p, c->qname.p, c->qual.p, c->cigar.p, c->tag_filter ? c->tag_drop.p : nullptr,
+                c->replace_rg_dev.p, c->replace_rg ? (uint32_t)c->replace_rg_id.size() : 0u, c->replace_rg ? 1u : 0u};
 }
+// the largest output record is bounded by the largest staged one + this (emit_stream adds the CIGAR operation of elp_clean_sam)
+static uint64_t out_growth(const elp_ctx *c) { return c->replace_rg ? 4 + (uint64_t)c->replace_rg_id.size() : 0; }
 
 int elp_emit_sorted_bam(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
   if (!c || !n_bytes_out) return ELP_ERR_ARG;
@@ -607,7 +654,7 @@ int elp_emit_sorted_bam(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_byte
   ELP_TRY(radix_check(c));
   if (c->raw_n != c->n) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bam: records were not staged with elp_stage_bam");
   const BamOut m = bam_out_of(c);
-  return emit_stream(c, m, m, nullptr, c->n - c->n_sr, c->max_raw_rec, out, cap, n_bytes_out);
+  return emit_stream(c, m, m, nullptr, c->n - c->n_sr, c->max_raw_rec + out_growth(c), out, cap, n_bytes_out);
 }
 
 // The same records as BGZF blocks (utils/bgzf/bgzf-files.go:324-383): members of at most 65280 input bytes, COMPRESSED on the device
@@ -622,7 +669,7 @@ int elp_emit_sorted_bgzf(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_byt
   ELP_TRY(radix_check(c));
   if (c->raw_n != c->n) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bgzf: records were not staged with elp_stage_bam");
   const BamOut m = bam_out_of(c);
-  return emit_stream(c, m, m, nullptr, c->n - c->n_sr, c->max_raw_rec, out, cap, n_bytes_out, true);
+  return emit_stream(c, m, m, nullptr, c->n - c->n_sr, c->max_raw_rec + out_growth(c), out, cap, n_bytes_out, true);
 }
 
 // MergeSortedFilesSplitPerChromosome (sam/split-merge.go:410-576) with payloads: the records of `groups` and of `spread` as ONE stream in
@@ -643,6 +690,10 @@ int elp_emit_merged_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t
   if (!groups || !spread || groups == spread || !n_bytes_out) return ELP_ERR_ARG;
   if (groups->derived.sorted_qname || spread->derived.sorted_qname) return merge_refuses_queryname(groups, "elp_emit_merged_bam");
   if (groups->raw_n != groups->n || spread->raw_n != spread->n) return set_error(groups, ELP_ERR_ARG, "elp_emit_merged_bam: records were not staged with elp_stage_bam");
+  // one stream, one filter: the tag filter (and the replacing read group) of `groups`, which `spread` must share
+  if (groups->tag_filter != spread->tag_filter || (groups->tag_filter && groups->h_tag_drop != spread->h_tag_drop))
+    return set_error(groups, ELP_ERR_ARG, "elp_emit_merged_bam: the two contexts' tag filters differ (elp_set_tag_filter)");
+  if (!same_replace_rg(groups, spread)) return set_error(groups, ELP_ERR_ARG, "elp_emit_merged_bam: the two contexts' replacing read groups differ (elp_set_replace_read_group)");
   uint64_t *slots = nullptr;
   ELP_TRY(merge_spread_slots(groups, spread, &slots));  // checks: both sorted, one device
   const uint64_t ng = groups->n - groups->n_sr, ns = spread->n - spread->n_sr, n_out = ng + ns;
@@ -656,8 +707,10 @@ int elp_emit_merged_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t
   if (ns) ELP_LAUNCH(groups, "merge_mark", k_merge_mark, dim3(blocks_for(ns, 256)), dim3(256), 0, ns, (const uint64_t *)slots, is_spread, src);
   ELP_TRY(exclusive_scan_u32(groups, is_spread, before, n_out, nullptr));
   ELP_LAUNCH(groups, "merge_fill", k_merge_fill, dim3(blocks_for(n_out, 256)), dim3(256), 0, n_out, (const uint32_t *)is_spread, (const uint32_t *)before, src);
-  const BamOut mg = bam_out_of(groups), ms = bam_out_of(spread);
-  return emit_stream(groups, mg, ms, src, n_out, std::max(groups->max_raw_rec, spread->max_raw_rec), out, cap, n_bytes_out);
+  const BamOut mg = bam_out_of(groups);
+  BamOut ms = bam_out_of(spread);
+  ms.drop = mg.drop; ms.rg_new = mg.rg_new;  // (equal contents, checked above; both on this device)
+  return emit_stream(groups, mg, ms, src, n_out, std::max(groups->max_raw_rec, spread->max_raw_rec) + out_growth(groups), out, cap, n_bytes_out);
 }
 
 }  // extern "C"

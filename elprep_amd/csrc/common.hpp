@@ -181,6 +181,14 @@ struct elp_ctx {
   elp::DVec<uint8_t> rg_ids;    // header read-group ids, concatenated (RG:Z -> rgid)
   elp::DVec<uint32_t> rg_ids_off;
   bool have_rg_ids = false;
+  // optional-field settings of a run (bam.hip: elp_set_tag_filter, elp_set_replace_read_group); elp_reset and elp_set_header clear both
+  static constexpr size_t TAG_WORDS = 65536 / 32;
+  bool tag_filter = false;             // tag_drop holds a table: bit k of it = fields with the 16-bit key k do not go out
+  std::vector<uint32_t> h_tag_drop;    // the host's copy (elp_emit_merged_bam compares the two contexts' tables)
+  elp::DVec<uint32_t> tag_drop;        // TAG_WORDS words in HBM
+  bool replace_rg = false;             // every record is of read group 0 and goes out with RG:Z:<replace_rg_id>
+  std::string replace_rg_id;
+  elp::DVec<uint8_t> replace_rg_dev;   // the id's bytes in HBM
   hipStream_t copy_stream = nullptr;
   elp::DVec<uint8_t> lut_dev;      // ApplyBQSR's dense LUT + covariate-present bytes uploaded ahead of elp_bqsr_apply (elp_bqsr_lut_upload)
   void *lut_pinned = nullptr;
@@ -492,6 +500,8 @@ int stage_reserve(elp_ctx *c, uint64_t n, uint64_t qb, uint64_t co, uint64_t sb,
 int merge_refuses_queryname(elp_ctx *groups, const char *who);  // filter.hip: ELP_ERR_UNSUPPORTED (cmd/merge.go:175-176)
 int merge_spread_slots(elp_ctx *groups, elp_ctx *spread, uint64_t **slots_out);  // filter.hip: the merge order as ranks, on the device  // grows the staged columns (ctx.hip)
 int stage_recode_seq(elp_ctx *c, uint64_t from, uint64_t bytes);
+inline void clear_run_settings(elp_ctx *c) { c->tag_filter = false; c->replace_rg = false; c->replace_rg_id.clear(); }  // elp_reset, elp_set_header
+inline bool same_replace_rg(const elp_ctx *a, const elp_ctx *b) { return a->replace_rg == b->replace_rg && a->replace_rg_id == b->replace_rg_id; }
 int stage_bam_columns(elp_ctx *c, uint32_t n_rec, uint64_t piece_bytes, uint64_t raw_end, uint64_t max_raw_rec, uint16_t split_id);  // bam.hip
 uint64_t bgzf_framed_size(uint64_t n_bytes);                                   // bgzf.hip
 int bgzf_frame(elp_ctx *c, const uint8_t *raw, uint64_t n_bytes, uint8_t *out);  // device to device, stored blocks

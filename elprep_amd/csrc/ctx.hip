@@ -320,6 +320,7 @@ int elp_set_header(elp_ctx *c, const elp_header *h) {
   ELP_HIP(c, hipSetDevice(c->device));
   c->n_ref = h->n_ref; c->n_rg = h->n_rg; c->n_lib = h->n_lib; c->n_cov = h->n_cov;
   c->derived.header_changed();  // (ApplyBQSR's records hold the read groups' covariates)
+  clear_run_settings(c);        // (the tag filter and the replacing read group belong to the run that set them)
   c->h_ref_len.assign(h->ref_len, h->ref_len + h->n_ref);
   c->h_rg_lib.assign(h->rg_lib, h->rg_lib + h->n_rg);
   c->h_rg_cov.assign(h->rg_cov, h->rg_cov + h->n_rg);
@@ -396,6 +397,7 @@ int elp_reset(elp_ctx *c) {
   c->max_qname_len = c->max_l_seq = 0;
   c->max_pos = 0;
   c->derived.records_changed();
+  clear_run_settings(c);
   return 0;
 }
 

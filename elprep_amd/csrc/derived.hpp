@@ -31,6 +31,8 @@ namespace elp {
 //   * elp_mark_duplicates rewrites FLAG's duplicate bit and raises no event: an existing coordinate permutation stays valid although
 //     the comparator reads FLAG (a host that wants the reference's order sorts behind mark duplicates; the bench's sort-ahead makes
 //     only the key passes early, the tie-break runs behind the final FLAGs).  Keys and scores do not read that bit.
+//     elp_clear_duplicate_flag, which takes the bit away in front of duplicate marking, does raise one (duplicate_bit_cleared: the marks
+//     and any permutation go - the comparator's modFlag tie-break read the bit; keys, the key passes made ahead and scores stay).
 //   * qual_changed() (elp_bqsr_apply) keeps the marks although they were decided with the scores of the old qualities: the marks are
 //     the result the reference computes BEFORE it recalibrates, not a cache of the current QUAL column.
 //   * header_changed() (elp_set_header) clears apply_recs only, although the keys hold n_ref and the marks the libraries: a header is
@@ -83,6 +85,7 @@ struct Derived {
   void qual_changed() { drop_scores(); drop_qual_hint(); }                                    // elp_bqsr_apply.  NOT the keys
   void flag_qual_restored() { fixed_fields_changed(); drop_qual_hint(); }                     // elp_rollback
   void split_changed() { drop_marked(); }                                                     // elp_split_classify
+  void duplicate_bit_cleared() { drop_sorted(); drop_marked(); }                              // elp_clear_duplicate_flag.  NOT keys / scores
   void radix_timed_out() { drop_sorted(); drop_marked(); }                                    // fetch_err: whichever sort it was, its result is wrong
   void qual_hint_refuted() { drop_qual_hint(); }                                              // the gather's retry path
   void header_changed() { apply_recs_valid = false; }                                         // elp_set_header

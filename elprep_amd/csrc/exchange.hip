@@ -264,6 +264,8 @@ static int copy_piece(elp_ctx *dst, elp_ctx *src, const uint32_t *idx, uint64_t 
   if (!dst->have_header || !src->have_header || dst->n_ref != src->n_ref || dst->n_rg != src->n_rg || dst->h_ref_len != src->h_ref_len)
     return set_error(dst, ELP_ERR_ARG, "elp_copy_records: the two contexts need the same header");
   if (new_split > 0xFFFF) return set_error(dst, ELP_ERR_ARG, "elp_copy_records: split id %d", new_split);
+  // (the copies' rgid column was made under the source's setting and their RG fields go out under the destination's)
+  if (!same_replace_rg(dst, src)) return set_error(dst, ELP_ERR_ARG, "elp_copy_records: the two contexts differ in their replacing read group (elp_set_replace_read_group)");
   if (n == 0) return 0;
   std::lock(dst->stage_mu, src->stage_mu);
   std::lock_guard<std::mutex> g1(dst->stage_mu, std::adopt_lock), g2(src->stage_mu, std::adopt_lock);
@@ -297,7 +299,14 @@ extern "C" int elp_exchange_records(elp_ctx *src, int send_peer, const uint32_t 
   if (!g || (send_peer >= 0 && (!src || (!idx && n))) || (recv_peer >= 0 && !dst)) return set_error(g, ELP_ERR_ARG, "elp_exchange_records: bad arguments");
   if (send_peer < 0) n = 0;
   if (new_split > 0xFFFF) return set_error(g, ELP_ERR_ARG, "elp_exchange_records: split id %d", new_split);
-  constexpr int HDR = 20;  // 0 records, 1-5 slice totals, 6-12 limits / counts (XC_*), 13 raw kind, 14 largest raw record, 15 magic, 16 status, 17 pieces, 18 piece
+  constexpr int HDR = 20;  // 0 records, 1-5 slice totals, 6-12 limits / counts (XC_*), 13 raw kind, 14 largest raw record, 15 magic, 16 status, 17 pieces, 18 piece,
+                           // 19 the sender's replacing read group (elp_set_replace_read_group) as a hash, 0 = none
+  auto rg_setting = [](const elp_ctx *c) -> uint64_t {
+    if (!c->replace_rg) return 0;
+    uint64_t h = 0xcbf29ce484222325ull;  // FNV-1a
+    for (unsigned char ch : c->replace_rg_id) h = (h ^ ch) * 0x100000001b3ull;
+    return h | 1ull;
+  };
   constexpr uint64_t MAGIC = 0x454c505845434847ull;
   uint64_t piece = 1;
   uint64_t out_pieces = 0;
@@ -340,6 +349,7 @@ extern "C" int elp_exchange_records(elp_ctx *src, int send_peer, const uint32_t 
       h_out[16] = (uint64_t)(uint32_t)(-st);
       h_out[17] = out_pieces;
       h_out[18] = j;
+      h_out[19] = rg_setting(src);
     }
     // ---- headers
     elp_ctx *sc = send_peer >= 0 ? src : dst;
@@ -358,6 +368,7 @@ extern "C" int elp_exchange_records(elp_ctx *src, int send_peer, const uint32_t 
       if (in_refuse) st = in_refuse;
       else if (h_in[15] != MAGIC || h_in[18] != j) st = set_error(g, ELP_ERR_DATA, "elp_exchange_records: rank %d did not send the header of piece %llu (calls out of step?)", recv_peer, (unsigned long long)j);
       else if (h_in[16]) st = set_error(g, -(int)(uint32_t)h_in[16], "elp_exchange_records: rank %d failed on its side of the exchange (status %d)", recv_peer, -(int)(uint32_t)h_in[16]);
+      else if (h_in[19] != rg_setting(dst)) st = set_error(g, ELP_ERR_ARG, "elp_exchange_records: rank %d's source and the destination differ in their replacing read group (elp_set_replace_read_group)", recv_peer);
       else {
         if (j == 0) in_pieces = std::max<uint64_t>(1, h_in[17]);
         R.n = h_in[0];

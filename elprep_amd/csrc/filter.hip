@@ -8,6 +8,9 @@
 //     metrics or BQSR.  Here one kernel evaluates the selected predicates for every staged record and marks the rejected ones in the
 //     record-state column (2 = filtered; 1 = sr-tagged copy, which still takes part in duplicate marking): every later stage skips
 //     them, the sort puts them behind the output (elp_num_sorted).
+//     RemoveNonExactMappingReadsStrict :115-134 reads optional fields (X0, X1, XM, XO, XG): a kernel of its own over the staged BAM
+//     records (elp_filter_exact_strict), same record states.  ClearDuplicateFlag :350-355 (elp_clear_duplicate_flag) rewrites the FLAG
+//     column in one streaming pass.
 // (2) `elprep split`: SplitFilePerChromosome's routing rule (sam/split-merge.go:280-293) per record — split of RNAME and the
 //     "spread" test — and the per-split record counts, so that a host can partition a staged file across GPUs without touching the
 //     payload on the CPU.
@@ -15,6 +18,7 @@
 //     the coordinate-sorted spread split goes among the concatenated, coordinate-sorted group splits (behind all group reads of
 //     its position).
 #include "common.hpp"
+#include "bamtag.hpp"
 
 namespace elp {
 
@@ -80,6 +84,82 @@ __global__ __launch_bounds__(256) void k_filter_records(FilterCols m, elp_predic
   const unsigned long long b = __ballot(drop), t = __ballot(tagged);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_dropped, (unsigned long long)__popcll(b));
   if ((threadIdx.x & 63) == 0 && t) atomicAdd(n_dropped + 1, (unsigned long long)__popcll(t));  // rejected tagged copies
+}
+
+// ---- RemoveNonExactMappingReadsStrict (filters/simple-filters.go:115-134): keep iff the FIRST field of key X0 exists and is 1, then
+// likewise X1, XM, XO, XG exist and are 0 - tested in this order, stopping at the first test that fails (TAGS.Get returns the first
+// entry of a key, utils/small-map.go:45-52).  A tested field that is no integer makes the reference panic on x.(int64).
+// One record per lane: a record's optional fields are a chain of dependent loads (every field's size is known only from its type byte
+// or its NUL), and 64 chains in flight per wave hide what one chain per wave would wait for; the lanes of a wave read neighbouring
+// records, whose tag areas lie a record's length apart.  The kernel writes verdicts only: the record states change in a second pass once
+// the call is known not to fail.
+struct StrictIn {
+  uint64_t n;
+  const uint8_t *raw;
+  const uint64_t *raw_off;  // per staged record: offset of its block_size field in raw
+  const uint8_t *state;
+  uint8_t *verdict;         // 0 keep, 1 reject
+};
+__global__ __launch_bounds__(256) void k_filter_exact_strict(StrictIn m, unsigned long long *cnt /* [0] rejected, [1] rejected tagged copies, [2] panics */) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool drop = false, tagged = false, panics = false;
+  if (i < m.n) {
+    uint8_t verdict = 0;
+    const uint8_t st = m.state[i];
+    if (st != 2) {
+      const uint8_t *p = m.raw + m.raw_off[i];
+      const uint32_t bs = ld_u32(p);
+      const uint8_t *rec = p + 4, *end = rec + bs;
+      const uint32_t l_name = rec[8], n_cig = ld_u16(rec + 12), l_seq = ld_u32(rec + 16);
+      const uint8_t *t = rec + (32ull + l_name + 4ull * n_cig + ((l_seq + 1) >> 1) + l_seq);
+      uint32_t found = 0, not_int = 0, wrong = 0;  // bit w: the first field of key w (X0 X1 XM XO XG) exists / is no integer / has another value
+      while (t + 3 <= end) {  // (staging has checked every record's fields: the walk ends at `end`)
+        const uint8_t k0 = t[0], k1 = t[1], ty = t[2];
+        const uint8_t *v = t + 3;
+        const uint32_t sz = tag_value_size(ty, v, end);
+        if (!sz) break;
+        if (k0 == 'X') {
+          const int w = k1 == '0' ? 0 : (k1 == '1' ? 1 : (k1 == 'M' ? 2 : (k1 == 'O' ? 3 : (k1 == 'G' ? 4 : -1))));
+          if (w >= 0 && !((found >> w) & 1u)) {
+            found |= 1u << w;
+            if (!tag_is_int(ty)) not_int |= 1u << w;
+            else if (tag_int_value(ty, v) != (w == 0 ? 1 : 0)) wrong |= 1u << w;
+          }
+        }
+        t = v + sz;
+      }
+      for (int w = 0; w < 5 && !verdict && !panics; w++) {
+        if (!((found >> w) & 1u)) verdict = 1;
+        else if ((not_int >> w) & 1u) panics = true;
+        else if ((wrong >> w) & 1u) verdict = 1;
+      }
+      if (verdict) { tagged = st == 1; drop = !tagged; }
+    }
+    m.verdict[i] = verdict;
+  }
+  const unsigned long long b = __ballot(drop), t = __ballot(tagged), e = __ballot(panics);
+  if ((threadIdx.x & 63) == 0) {
+    if (b) atomicAdd(cnt, (unsigned long long)__popcll(b));
+    if (t) atomicAdd(cnt + 1, (unsigned long long)__popcll(t));
+    if (e) atomicAdd(cnt + 2, (unsigned long long)__popcll(e));
+  }
+}
+__global__ __launch_bounds__(256) void k_reject_marked(uint64_t n, const uint8_t *__restrict__ verdict, uint8_t *__restrict__ state) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && verdict[i]) state[i] = 2;
+}
+
+// ---- ClearDuplicateFlag (filters/simple-filters.go:350-355): FLAG &^= 0x400 on every record; eight flags per 16-byte access
+__global__ __launch_bounds__(256) void k_clear_duplicate_flag(uint64_t n, uint16_t *__restrict__ flag) {
+  const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (uint64_t)gridDim.x * blockDim.x, nv = n >> 3;
+  uint4 *v = reinterpret_cast<uint4 *>(flag);  // (a column starts at an allocation's start: 16-byte aligned)
+  constexpr uint32_t KEEP = ~(((uint32_t)F_DUPLICATE << 16) | (uint32_t)F_DUPLICATE);
+  for (uint64_t j = gid; j < nv; j += stride) {
+    uint4 x = v[j];
+    x.x &= KEEP; x.y &= KEEP; x.z &= KEEP; x.w &= KEEP;
+    v[j] = x;
+  }
+  if (gid < (n & 7)) flag[nv * 8 + gid] &= (uint16_t)~F_DUPLICATE;
 }
 
 // ---- split: routing rule of SplitFilePerChromosome
@@ -382,6 +462,49 @@ int elp_filter_records(elp_ctx *c, const elp_predicates *p, uint64_t *n_dropped_
   c->n_filtered += dropped + dropped_tagged;  // state-2 records of either origin: none of them is a duplicate-marking candidate
   c->derived.fixed_fields_changed();  // (the has_sr column)
   if (n_dropped_out) *n_dropped_out = dropped;
+  return 0;
+}
+
+int elp_filter_exact_strict(elp_ctx *c, uint64_t *n_rejected_out) {
+  if (!c) return ELP_ERR_ARG;
+  ELP_HIP(c, hipSetDevice(c->device));
+  if (c->raw_n != c->n) return set_error(c, ELP_ERR_ARG, "elp_filter_exact_strict: records were not staged with elp_stage_bam / elp_stage_bgzf (column-staged records have no optional fields)");
+  if (n_rejected_out) *n_rejected_out = 0;
+  const uint64_t n = c->n;
+  if (!n) return 0;
+  uint8_t *verdict;
+  unsigned long long *cnt;
+  ELP_TRY(scratch(c, 5, n + 64, &verdict));
+  ELP_TRY(scratch(c, 6, 4, &cnt));
+  ELP_HIP(c, hipMemsetAsync(cnt, 0, 24, c->stream));
+  StrictIn m{n, c->raw.p, c->raw_off.p, c->has_sr.p, verdict};
+  ELP_LAUNCH(c, "filter_exact_strict", k_filter_exact_strict, dim3(blocks_for(n, 256)), dim3(256), 0, m, cnt);
+  unsigned long long h[3] = {0, 0, 0};
+  ELP_HIP(c, hipMemcpyAsync(h, cnt, 24, hipMemcpyDeviceToHost, c->stream));
+  ELP_HIP(c, elp::stream_wait(c->stream));
+  // (a failed call leaves the record states as they were)
+  if (h[2]) return set_error(c, ELP_ERR_DATA, "elp_filter_exact_strict: %llu record(s) hold an X0 / X1 / XM / XO / XG field that is no integer "
+                             "(reference: panic on x.(int64), filters/simple-filters.go:117-131)", h[2]);
+  if (h[0] + h[1]) {
+    ELP_LAUNCH(c, "filter_exact_strict_mark", k_reject_marked, dim3(blocks_for(n, 256)), dim3(256), 0, n, (const uint8_t *)verdict, c->has_sr.p);
+    ELP_HIP(c, elp::stream_wait(c->stream));
+  }
+  c->n_sr += h[0];             // as elp_filter_records: they leave the output like the tagged copies do
+  c->n_filtered += h[0] + h[1];
+  c->derived.fixed_fields_changed();  // (the has_sr column)
+  if (n_rejected_out) *n_rejected_out = h[0];
+  return 0;
+}
+
+int elp_clear_duplicate_flag(elp_ctx *c) {
+  if (!c) return ELP_ERR_ARG;
+  ELP_HIP(c, hipSetDevice(c->device));
+  if (c->n) {
+    const unsigned grid = std::max(1u, std::min(blocks_for((c->n + 7) / 8, 256), (unsigned)c->n_cu * 8));
+    ELP_LAUNCH(c, "clear_duplicate_flag", k_clear_duplicate_flag, dim3(grid), dim3(256), 0, c->n, c->flag.p);
+    ELP_HIP(c, elp::stream_wait(c->stream));
+  }
+  c->derived.duplicate_bit_cleared();
   return 0;
 }
 

@@ -238,6 +238,48 @@ class Engine:
         del keep
         return int(n.value)
 
+    # ---- the options that touch optional fields (include/elprep_hip.h)
+    @staticmethod
+    def _tag_keys(keys, word):
+        """a key list as (bytes, count) for elp_set_tag_filter; `word` ("all" / "none") = the list's special value, None = no filter.
+        Entries that are not two bytes long cannot match a BAM tag key and are dropped here, as the header asks of the host."""
+        if keys is None:
+            return None, 0 if word == "all" else -1
+        if isinstance(keys, (str, bytes)):
+            if keys in (word, word.encode()):
+                return None, -1 if word == "all" else 0
+            keys = [keys]
+        enc = [k.encode() if isinstance(k, str) else bytes(k) for k in keys]
+        enc = [k for k in enc if len(k) == 2]
+        if not enc and word == "all":
+            return None, 0
+        return b"".join(enc), len(enc)
+
+    def set_tag_filter(self, remove=None, keep=None):
+        """--remove-optional-fields / --keep-optional-fields for the emitters (elp_set_tag_filter).  remove: a list of two-character
+        keys (str or bytes), "all", or None; keep: a list, "none", or None (no keep filter)"""
+        rb, rn = self._tag_keys(remove, "all")
+        kb, kn = self._tag_keys(keep, "none")
+        ra = np.frombuffer(rb, dtype=np.uint8) if rb else None
+        ka = np.frombuffer(kb, dtype=np.uint8) if kb else None
+        self._check(self.L.elp_set_tag_filter(self.h, _vp(ra), rn, _vp(ka), kn))
+
+    def set_replace_read_group(self, id):
+        """--replace-read-group: every record staged from BAM bytes from now on belongs to the header's one read group and is emitted
+        with RG:Z:<id> (elp_set_replace_read_group)"""
+        b = id.encode() if isinstance(id, str) else bytes(id)
+        self._check(self.L.elp_set_replace_read_group(self.h, b, len(b)))
+
+    def filter_exact_strict(self) -> int:
+        """RemoveNonExactMappingReadsStrict on the staged BAM records (elp_filter_exact_strict) -> number of records rejected by this call"""
+        n = C.c_uint64()
+        self._check(self.L.elp_filter_exact_strict(self.h, C.byref(n)))
+        return int(n.value)
+
+    def clear_duplicate_flag(self):
+        """ClearDuplicateFlag: FLAG &^= 0x400 on every staged record (elp_clear_duplicate_flag)"""
+        self._check(self.L.elp_clear_duplicate_flag(self.h))
+
     def copy_records_from(self, src: "Engine", idx: np.ndarray, new_split: Optional[int] = None, tag_sr=False):
         """appends src's records idx (staging indices) to this context, device to device (elp_copy_records).  tag_sr: False / True (all
         copies tagged sr) / 2 (the copies whose index has bit 31 set)"""

@@ -164,6 +164,50 @@ int elp_emit_sorted_bgzf(elp_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *n_b
  * order (elp_merge_spread's slots), gathered in HBM.  Both contexts staged with elp_stage_bam, coordinate-sorted, on one device. */
 int elp_emit_merged_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out);
 
+/* ---- the options that touch a record's optional fields (filters/simple-filters.go; cmd/filter.go:696-902) ----
+ * The settings of elp_set_tag_filter and elp_set_replace_read_group belong to a run: elp_reset and elp_set_header clear both.
+ *
+ * elp_set_tag_filter: `--remove-optional-fields a,b` / `all` (RemoveOptionalFields :235-257, KeepOptionalFields(nil) :263-269,
+ *   cmd/filter.go:878-889) and `--keep-optional-fields a,b` / `none` (KeepOptionalFields :261-288, cmd/filter.go:891-902) for the
+ *   emitters.  remove_keys = n_remove two-byte keys behind each other; n_remove = -1: `all`; 0: no such filter.  keep_keys likewise;
+ *   n_keep = -1: no keep filter; 0: `none` (also what a keep list without any two-byte entry amounts to).  A BAM tag key is two bytes,
+ *   so a list entry of another length matches no field: the host drops it from the list.  More than 4096 keys in a list:
+ *   ELP_ERR_UNSUPPORTED.  filters2 applies remove, then keep, each by SmallMap.DeleteIf, which deletes EVERY entry that matches
+ *   (utils/small-map.go:89-99): a field goes out iff its key is not in the remove list (and remove is not `all`) and, with a keep
+ *   filter, its key is in the keep list; fields of one key are all treated alike, the survivors keep their order and are re-encoded as
+ *   before.  Call any time before the emit call (n_remove = 0, n_keep = -1 takes the filter away).  It acts on elp_emit_sorted_bam,
+ *   elp_emit_sorted_bgzf and elp_emit_merged_bam - sizes, offsets, block_size, the size query, BGZF framing; the merged stream takes the
+ *   filter of `groups` and the call returns ELP_ERR_ARG if `spread`'s differs.  Nothing else sees it (filters2 runs behind ApplyBQSR,
+ *   cmd/filter.go:66-100): the staged rgid column and sr states, duplicate marking, BQSR, elp_copy_records and elp_exchange_records work
+ *   on the unfiltered records; removing RG from the output changes no table.  Malformed fields and H fields are reported as without a
+ *   filter, also in a field the filter drops (the reference parses before it filters).  Reads: the staged BAM bytes.  Writes: a table of
+ *   65536 bits (one per key) in HBM, which the emitters' size and gather kernels look up per field in the walk they make anyway.
+ * elp_set_replace_read_group: `--replace-read-group` (AddOrReplaceReadGroup :156-162).  Call after elp_set_header with a header of ONE
+ *   read group (the new one: header.RG = []{readGroup}) and before staging (ELP_ERR_ARG with records staged or n_rg != 1); id_len <= 255,
+ *   no NUL inside.  From then on elp_stage_bam / elp_stage_bgzf do not look RG fields up (elp_set_read_group_ids is not needed): every
+ *   record, with or without an RG field, gets rgid 0 (aln.SetRG(id) runs on every alignment in front of AddREFID and MarkDuplicates:
+ *   library and BQSR covariate are the new group's).  The emitters follow SmallMap.Set (utils/small-map.go:59-67): the first field
+ *   with key RG, whatever its type, goes out as RG:Z:<id> in its place, later RG fields stay as they are, a record without one gets
+ *   RG:Z:<id> behind its last field; the tag filter then acts on the result.  An output record can be 4 + id_len bytes longer than the
+ *   staged one (the size query accounts for it).  The setting travels with nothing: elp_copy_records / elp_exchange_records between
+ *   contexts whose settings differ return ELP_ERR_ARG, as does elp_emit_merged_bam.  Writes: the rgid column (at staging).
+ * elp_filter_exact_strict: `--filter-non-exact-mapping-reads-strict` (RemoveNonExactMappingReadsStrict :115-134), one of the filters1
+ *   predicates - call where elp_filter_records is called.  A record is kept iff its FIRST field of key X0 exists and is 1, then likewise
+ *   X1, XM, XO, XG exist and are 0, in this order, stopping at the first test that fails; the value is the integer parseBamAlignment
+ *   reads (types c C s S i I, sam/bam-files.go:138-173).  A tested field of another type makes the reference panic (x.(int64)): the call
+ *   fails with ELP_ERR_DATA and changes nothing - but only if the tests in front of it passed for that record.  Rejected records get
+ *   the state elp_filter_records gives (same effect on everything that follows; the counts of the calls add up).  Needs records staged
+ *   with elp_stage_bam / elp_stage_bgzf (ELP_ERR_ARG otherwise: column-staged records have no optional fields).  Reads: the staged BAM
+ *   bytes, the record-state column.  Writes: the record-state column.  n_rejected_out may be NULL.
+ * elp_clear_duplicate_flag: `--clear-duplicate-flag` (ClearDuplicateFlag :350-355, cmd/filter.go:729-731): FLAG &^= 0x400 on every
+ *   staged record whatever its state, behind the filters1 predicates and in front of elp_mark_duplicates.  Existing duplicate marks and
+ *   any permutation become invalid (the comparator's modFlag tie-break reads the bit); sort keys and scores stay.  Reads and writes: the
+ *   FLAG column. */
+int elp_set_tag_filter(elp_ctx *ctx, const uint8_t *remove_keys, int n_remove, const uint8_t *keep_keys, int n_keep);
+int elp_set_replace_read_group(elp_ctx *ctx, const uint8_t *id, int id_len);
+int elp_filter_exact_strict(elp_ctx *ctx, uint64_t *n_rejected_out /* may be NULL */);
+int elp_clear_duplicate_flag(elp_ctx *ctx);
+
 /* ---- fused per-record predicates: filters/simple-filters.go ----
  * The filters that stand in front of MarkDuplicates in filters1 (cmd/filter.go:696-803), evaluated in one pass over the staged
  * records: a rejected record takes part in nothing that follows (duplicate marking, sort output, metrics, BQSR tables) - it is
