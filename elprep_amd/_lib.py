@@ -26,7 +26,7 @@ HIP_SYMBOLS = [
     "elp_dup_metrics", "elp_dup_metrics_hist", "elp_bqsr_set_reference", "elp_bqsr_set_known_sites", "elp_bqsr_gather", "elp_bqsr_apply", "elp_get_qual",
     "elp_bqsr_gather_device", "elp_bqsr_tables_fetch", "elp_bqsr_quals_counted", "elp_bqsr_tables_fetch_rows", "elp_bqsr_lut_upload_rows", "elp_group_unique_id", "elp_group_init", "elp_group_rank", "elp_group_size",
     "elp_bqsr_tables_add", "elp_bqsr_tables_allreduce", "elp_allreduce_i64",
-    "elp_filter_records", "elp_clean_sam", "elp_set_tag_filter", "elp_set_replace_read_group", "elp_filter_exact_strict", "elp_clear_duplicate_flag", "elp_split_classify", "elp_merge_spread",
+    "elp_filter_records", "elp_clean_sam", "elp_set_tag_filter", "elp_set_replace_read_group", "elp_filter_exact_strict", "elp_clear_duplicate_flag", "elp_replace_reference_dictionary", "elp_split_classify", "elp_merge_spread",
     "elp_set_read_group_ids", "elp_pinned_alloc", "elp_pinned_free", "elp_stage_bam", "elp_emit_sorted_bam", "elp_stage_bgzf", "elp_emit_sorted_bgzf",
     "elp_set_header_columns", "elp_stage_columns", "elp_set_read_group_ids_flat", "elp_filter_records_flat", "elp_group_probe", "elp_group_init_transport", "elp_copy_records", "elp_exchange_records", "elp_group_set_p2p", "elp_group_share", "elp_emit_merged_bam", "elp_bqsr_lut_upload",
     "elp_snapshot", "elp_rollback", "elp_set_tuning", "elp_profile_enable", "elp_profile_reset", "elp_profile_count", "elp_profile_get", "elp_debug_check_guards",
@@ -34,7 +34,7 @@ HIP_SYMBOLS = [
 HOST_SYMBOLS = [
     "elp_bqsr_tables_new", "elp_bqsr_tables_new_rows", "elp_bqsr_tables_free", "elp_bqsr_tables_merge", "elp_bqsr_tables_finalize", "elp_bqsr_tables_empirical",
     "elp_bqsr_tables_combined", "elp_bqsr_tables_quantize", "elp_bqsr_tables_build_lut", "elp_bqsr_tables_build_lut_rows", "elp_bqsr_tables_report", "elp_host_free",
-    "elp_dup_derived", "elp_dup_metrics_report", "elp_dup_metrics_report_hist",
+    "elp_dup_derived", "elp_dup_metrics_report", "elp_dup_metrics_report_hist", "elp_host_dictionary_map",
 ]
 
 
@@ -95,10 +95,11 @@ def hip() -> C.CDLL:
         L.elp_stage_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint16]
         L.elp_filter_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.elp_clean_sam.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-        # (an older build named by ELP_HIP_SO for A/B timing lacks these four; calling one of them there still fails, with AttributeError)
+        # (an older build named by ELP_HIP_SO for A/B timing lacks these five; calling one of them there still fails, with AttributeError)
         for name, args in (("elp_set_tag_filter", [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
                            ("elp_set_replace_read_group", [C.c_void_p, C.c_char_p, C.c_int]),
-                           ("elp_filter_exact_strict", [C.c_void_p, C.POINTER(C.c_uint64)]), ("elp_clear_duplicate_flag", [C.c_void_p])):
+                           ("elp_filter_exact_strict", [C.c_void_p, C.POINTER(C.c_uint64)]), ("elp_clear_duplicate_flag", [C.c_void_p]),
+                           ("elp_replace_reference_dictionary", [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_uint64)])):
             if ELP_AB_BUILD and not hasattr(L, name):
                 continue
             getattr(L, name).argtypes = args
@@ -163,5 +164,6 @@ def host() -> C.CDLL:
         L.elp_dup_metrics_report.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_char_p]
         L.elp_dup_metrics_report_hist.restype = C.c_void_p
         L.elp_dup_metrics_report_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_char_p]
+        L.elp_host_dictionary_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int)]
         _host = L
     return _host

@@ -494,6 +494,7 @@ int elp_stage_bam(elp_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint
   std::lock_guard<std::mutex> g(c->stage_mu);
   ELP_HIP(c, hipSetDevice(c->device));
   if (!c->have_header) return set_error(c, ELP_ERR_ARG, "elp_stage_bam: call elp_set_header first");
+  if (c->dict_replaced) return staging_refused_after_replace(c, "elp_stage_bam");
   if (c->n_rg && !c->have_rg_ids && !c->replace_rg) return set_error(c, ELP_ERR_ARG, "elp_stage_bam: call elp_set_read_group_ids first");
   if (c->n != c->raw_n) return set_error(c, ELP_ERR_ARG, "elp_stage_bam: the context already holds records staged with elp_stage");
   hipStream_t st = c->stream;
@@ -694,6 +695,8 @@ int elp_emit_merged_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t
   if (groups->tag_filter != spread->tag_filter || (groups->tag_filter && groups->h_tag_drop != spread->h_tag_drop))
     return set_error(groups, ELP_ERR_ARG, "elp_emit_merged_bam: the two contexts' tag filters differ (elp_set_tag_filter)");
   if (!same_replace_rg(groups, spread)) return set_error(groups, ELP_ERR_ARG, "elp_emit_merged_bam: the two contexts' replacing read groups differ (elp_set_replace_read_group)");
+  if (groups->dict_replaced != spread->dict_replaced)
+    return set_error(groups, ELP_ERR_ARG, "elp_emit_merged_bam: one context has replaced its reference dictionary, the other has not (elp_replace_reference_dictionary)");
   uint64_t *slots = nullptr;
   ELP_TRY(merge_spread_slots(groups, spread, &slots));  // checks: both sorted, one device
   const uint64_t ng = groups->n - groups->n_sr, ns = spread->n - spread->n_sr, n_out = ng + ns;

@@ -1030,6 +1030,7 @@ extern "C" int elp_stage_bgzf(elp_ctx *c, const uint8_t *bgzf, uint64_t n_bytes,
   std::lock_guard<std::mutex> g(c->stage_mu);
   ELP_HIP(c, hipSetDevice(c->device));
   if (!c->have_header) return set_error(c, ELP_ERR_ARG, "elp_stage_bgzf: call elp_set_header first");
+  if (c->dict_replaced) return staging_refused_after_replace(c, "elp_stage_bgzf");
   if (c->n_rg && !c->have_rg_ids && !c->replace_rg) return set_error(c, ELP_ERR_ARG, "elp_stage_bgzf: call elp_set_read_group_ids first");
   if (c->n != c->raw_n) return set_error(c, ELP_ERR_ARG, "elp_stage_bgzf: the context already holds records staged with elp_stage");
   // ---- the blocks (host: a few fields per 64 KB; utils/bgzf/bgzf-files.go:95-123)

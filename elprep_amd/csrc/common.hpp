@@ -80,6 +80,11 @@ struct elp_ctx {
   std::vector<uint16_t> h_rg_lib, h_rg_cov;
   elp::DVec<int32_t> ref_len;
   elp::DVec<uint16_t> rg_lib, rg_cov;
+  // elp_replace_reference_dictionary (filter.hip): n_ref / h_ref_len / ref_len above hold the NEW dictionary while dict_replaced; the one
+  // elp_set_header gave is kept here, elp_reset returns to it (the staged bytes of the next file carry the header's refids again)
+  bool dict_replaced = false;
+  int32_t n_ref0 = 0;
+  std::vector<int32_t> h_ref_len0;
 
   // staged columns
   static constexpr uint64_t SEQ_FRONT = 16;  // the SEQ column starts this many bytes into its allocation: the per-base kernels load the
@@ -502,6 +507,11 @@ int merge_spread_slots(elp_ctx *groups, elp_ctx *spread, uint64_t **slots_out); 
 int stage_recode_seq(elp_ctx *c, uint64_t from, uint64_t bytes);
 inline void clear_run_settings(elp_ctx *c) { c->tag_filter = false; c->replace_rg = false; c->replace_rg_id.clear(); }  // elp_reset, elp_set_header
 inline bool same_replace_rg(const elp_ctx *a, const elp_ctx *b) { return a->replace_rg == b->replace_rg && a->replace_rg_id == b->replace_rg_id; }
+// ctx.hip: the context's reference table becomes (n_ref, ref_len) - host copy, device copy, the per-refid BQSR vectors resized and cleared
+// (references and known sites set under the old refids are released)
+int install_dictionary(elp_ctx *c, int32_t n_ref, const int32_t *ref_len);
+// staging into a context whose dictionary was replaced: its columns hold new refids, the bytes to come the header's
+int staging_refused_after_replace(elp_ctx *c, const char *who);
 int stage_bam_columns(elp_ctx *c, uint32_t n_rec, uint64_t piece_bytes, uint64_t raw_end, uint64_t max_raw_rec, uint16_t split_id);  // bam.hip
 uint64_t bgzf_framed_size(uint64_t n_bytes);                                   // bgzf.hip
 int bgzf_frame(elp_ctx *c, const uint8_t *raw, uint64_t n_bytes, uint8_t *out);  // device to device, stored blocks

@@ -239,6 +239,39 @@ int radix_check(elp_ctx *c) {
   return fetch_err(c, e);
 }
 
+// the references and known sites set so far are released (they are keyed by refids of a dictionary that goes)
+int release_bqsr_inputs(elp_ctx *c) {
+  ELP_HIP(c, elp::stream_wait(c->stream));  // (nothing queued reads the contigs that are released below)
+  for (auto &p : c->h_ref_seq) if (p) { (void)hipFree(p); p = nullptr; }
+  for (auto &p : c->h_sites) if (p) { (void)hipFree(p); p = nullptr; }
+  for (auto &p : c->h_site_idx) if (p) { (void)hipFree(p); p = nullptr; }
+  for (auto &v : c->h_ref_seq_len) v = 0;
+  for (auto &v : c->h_n_sites) v = 0;
+  c->bqsr_ptrs_dirty = true;
+  return 0;
+}
+int install_dictionary(elp_ctx *c, int32_t n_ref, const int32_t *ref_len) {
+  ELP_TRY(ensure(c, c->ref_len, (size_t)n_ref + 1));
+  ELP_TRY(release_bqsr_inputs(c));
+  const std::vector<int32_t> len(ref_len, ref_len + n_ref);  // (ref_len may be the context's own copy)
+  c->n_ref = n_ref;
+  c->h_ref_len = len;
+  if (n_ref) ELP_HIP(c, hipMemcpyAsync(c->ref_len.p, c->h_ref_len.data(), (size_t)n_ref * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  ELP_HIP(c, elp::stream_wait(c->stream));
+  c->h_ref_seq.assign((size_t)n_ref, nullptr);
+  c->h_ref_seq_len.assign((size_t)n_ref, 0);
+  c->h_sites.assign((size_t)n_ref, nullptr);
+  c->h_site_idx.assign((size_t)n_ref, nullptr);
+  c->h_n_sites.assign((size_t)n_ref, 0);
+  c->ref_flags_dirty.assign((size_t)n_ref, 0);
+  c->bqsr_ptrs_dirty = true;
+  return 0;
+}
+int staging_refused_after_replace(elp_ctx *c, const char *who) {
+  return set_error(c, ELP_ERR_ARG, "%s: the reference dictionary was replaced (elp_replace_reference_dictionary): the staged refids are the new "
+                   "dictionary's, the header's are the old one's; call elp_reset or elp_set_header first", who);
+}
+
 }  // namespace elp
 
 using namespace elp;
@@ -318,10 +351,16 @@ int elp_set_header(elp_ctx *c, const elp_header *h) {
   if (!c || !h || h->n_ref < 0 || h->n_rg < 0 || (h->n_ref && !h->ref_len) || (h->n_rg && (!h->rg_lib || !h->rg_cov)))
     return set_error(c, ELP_ERR_ARG, "elp_set_header: bad arguments");
   ELP_HIP(c, hipSetDevice(c->device));
+  // references and known sites set under a replaced dictionary are keyed by ITS refids: they do not pass into the new header's numbering
+  // (as elp_reset releases them; without a replacement they stay, refid by refid, as they always did)
+  if (c->dict_replaced) ELP_TRY(release_bqsr_inputs(c));
   c->n_ref = h->n_ref; c->n_rg = h->n_rg; c->n_lib = h->n_lib; c->n_cov = h->n_cov;
   c->derived.header_changed();  // (ApplyBQSR's records hold the read groups' covariates)
   clear_run_settings(c);        // (the tag filter and the replacing read group belong to the run that set them)
   c->h_ref_len.assign(h->ref_len, h->ref_len + h->n_ref);
+  c->n_ref0 = h->n_ref;          // (the dictionary elp_reset returns to behind elp_replace_reference_dictionary)
+  c->h_ref_len0 = c->h_ref_len;
+  c->dict_replaced = false;
   c->h_rg_lib.assign(h->rg_lib, h->rg_lib + h->n_rg);
   c->h_rg_cov.assign(h->rg_cov, h->rg_cov + h->n_rg);
   for (int i = 0; i < h->n_rg; i++) {
@@ -398,6 +437,12 @@ int elp_reset(elp_ctx *c) {
   c->max_pos = 0;
   c->derived.records_changed();
   clear_run_settings(c);
+  if (c->dict_replaced) {  // back to the header's dictionary: the next file's bytes carry its refids
+    ELP_HIP(c, hipSetDevice(c->device));
+    ELP_TRY(install_dictionary(c, c->n_ref0, c->h_ref_len0.data()));
+    c->derived.header_changed();
+    c->dict_replaced = false;
+  }
   return 0;
 }
 
@@ -410,6 +455,7 @@ int elp_stage(elp_ctx *c, const elp_batch *b) {
   std::lock_guard<std::mutex> g(c->stage_mu);
   ELP_HIP(c, hipSetDevice(c->device));
   if (!c->have_header) return set_error(c, ELP_ERR_ARG, "elp_stage: call elp_set_header first");
+  if (c->dict_replaced) return staging_refused_after_replace(c, "elp_stage");
   uint64_t n = b->n;
   if (n == 0) return 0;
   if (c->n + n > 0xFFFFFFF0ull) return set_error(c, ELP_ERR_UNSUPPORTED, "more than 2^32-16 records per context");

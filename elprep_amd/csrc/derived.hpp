@@ -21,7 +21,8 @@ namespace elp {
 //   presort: the sort's key passes made ahead        the key column (keys)
 //   marks: FLAG's duplicate bit, mate, pair_win      keys (upos), scores, REFID, FLAG, rgid -> library, split ids, QNAME
 //   quality hint: qual_present                       QUAL (a sample, or the score kernel's), tuning "qual_hint", "qual_hint_drop"
-//   snapshot: snap_flag, snap_qual                   a copy of FLAG and QUAL of the n records staged when it was taken
+//   snapshot: snap_flag, snap_qual                   a copy of FLAG and QUAL of the n records staged when it was taken, under the
+//                                                    dictionary (REFID, RNEXT numbering, n_ref) in force at that time
 //   tile index: tile_first                           the QUAL offsets (n, qual_bytes)
 //   one-length fact: uniform_len                     the QUAL and SEQ offsets, l_seq (n, qual_bytes)
 //
@@ -37,7 +38,10 @@ namespace elp {
 //     the result the reference computes BEFORE it recalibrates, not a cache of the current QUAL column.
 //   * header_changed() (elp_set_header) clears apply_recs only, although the keys hold n_ref and the marks the libraries: a header is
 //     set before records are staged (elp_stage refuses without one), and staging clears everything.
-//   * No event clears the snapshot but records_changed(): it is a copy to return to, not a function of the current columns.
+//   * No event clears the snapshot but records_changed() and dictionary_replaced(): it is a copy to return to, not a function of the
+//     current columns.  dictionary_replaced() (elp_replace_reference_dictionary) rewrites REFID / RNEXT, the record states and n_ref: what
+//     fixed_fields_changed() and header_changed() spoil goes (the keys with the key passes made ahead of them, scores, permutation,
+//     marks, ApplyBQSR's records), and the snapshot too - a rollback restores FLAG and QUAL, not the refids they were decided under.
 //   * Tuning "score_kernel" clears the scores only (with one `adapted` flag it took the keys along, which do not depend on it).
 struct Derived {
   bool keys = false;
@@ -86,6 +90,7 @@ struct Derived {
   void flag_qual_restored() { fixed_fields_changed(); drop_qual_hint(); }                     // elp_rollback
   void split_changed() { drop_marked(); }                                                     // elp_split_classify
   void duplicate_bit_cleared() { drop_sorted(); drop_marked(); }                              // elp_clear_duplicate_flag.  NOT keys / scores
+  void dictionary_replaced() { fixed_fields_changed(); header_changed(); have_snapshot = false; }  // elp_replace_reference_dictionary: REFID, RNEXT, has_sr, n_ref
   void radix_timed_out() { drop_sorted(); drop_marked(); }                                    // fetch_err: whichever sort it was, its result is wrong
   void qual_hint_refuted() { drop_qual_hint(); }                                              // the gather's retry path
   void header_changed() { apply_recs_valid = false; }                                         // elp_set_header

@@ -266,6 +266,9 @@ static int copy_piece(elp_ctx *dst, elp_ctx *src, const uint32_t *idx, uint64_t 
   if (new_split > 0xFFFF) return set_error(dst, ELP_ERR_ARG, "elp_copy_records: split id %d", new_split);
   // (the copies' rgid column was made under the source's setting and their RG fields go out under the destination's)
   if (!same_replace_rg(dst, src)) return set_error(dst, ELP_ERR_ARG, "elp_copy_records: the two contexts differ in their replacing read group (elp_set_replace_read_group)");
+  // (a replaced dictionary renumbers the columns: the refids of one side would be read under the other's dictionary)
+  if (dst->dict_replaced != src->dict_replaced)
+    return set_error(dst, ELP_ERR_ARG, "elp_copy_records: one context has replaced its reference dictionary, the other has not (elp_replace_reference_dictionary)");
   if (n == 0) return 0;
   std::lock(dst->stage_mu, src->stage_mu);
   std::lock_guard<std::mutex> g1(dst->stage_mu, std::adopt_lock), g2(src->stage_mu, std::adopt_lock);
@@ -300,12 +303,14 @@ extern "C" int elp_exchange_records(elp_ctx *src, int send_peer, const uint32_t 
   if (send_peer < 0) n = 0;
   if (new_split > 0xFFFF) return set_error(g, ELP_ERR_ARG, "elp_exchange_records: split id %d", new_split);
   constexpr int HDR = 20;  // 0 records, 1-5 slice totals, 6-12 limits / counts (XC_*), 13 raw kind, 14 largest raw record, 15 magic, 16 status, 17 pieces, 18 piece,
-                           // 19 the sender's replacing read group (elp_set_replace_read_group) as a hash, 0 = none
+                           // 19 the sender's replacing read group (elp_set_replace_read_group) as a hash, 0 = none; bit 1 of the word: the sender
+                           //    has replaced its reference dictionary (elp_replace_reference_dictionary)
   auto rg_setting = [](const elp_ctx *c) -> uint64_t {
-    if (!c->replace_rg) return 0;
+    const uint64_t dict = c->dict_replaced ? 2ull : 0ull;
+    if (!c->replace_rg) return dict;
     uint64_t h = 0xcbf29ce484222325ull;  // FNV-1a
     for (unsigned char ch : c->replace_rg_id) h = (h ^ ch) * 0x100000001b3ull;
-    return h | 1ull;
+    return ((h | 1ull) & ~2ull) | dict;
   };
   constexpr uint64_t MAGIC = 0x454c505845434847ull;
   uint64_t piece = 1;
@@ -368,6 +373,7 @@ extern "C" int elp_exchange_records(elp_ctx *src, int send_peer, const uint32_t 
       if (in_refuse) st = in_refuse;
       else if (h_in[15] != MAGIC || h_in[18] != j) st = set_error(g, ELP_ERR_DATA, "elp_exchange_records: rank %d did not send the header of piece %llu (calls out of step?)", recv_peer, (unsigned long long)j);
       else if (h_in[16]) st = set_error(g, -(int)(uint32_t)h_in[16], "elp_exchange_records: rank %d failed on its side of the exchange (status %d)", recv_peer, -(int)(uint32_t)h_in[16]);
+      else if ((h_in[19] ^ rg_setting(dst)) & 2ull) st = set_error(g, ELP_ERR_ARG, "elp_exchange_records: of rank %d's source and the destination one has replaced its reference dictionary, the other has not (elp_replace_reference_dictionary)", recv_peer);
       else if (h_in[19] != rg_setting(dst)) st = set_error(g, ELP_ERR_ARG, "elp_exchange_records: rank %d's source and the destination differ in their replacing read group (elp_set_replace_read_group)", recv_peer);
       else {
         if (j == 0) in_pieces = std::max<uint64_t>(1, h_in[17]);

@@ -144,6 +144,7 @@ class Engine:
 
     def reset(self):
         self._check(self.L.elp_reset(self.h))
+        self._n_ref_now = None  # (elp_reset returns to the header's dictionary)
 
     def snapshot(self):
         self._check(self.L.elp_snapshot(self.h))
@@ -279,6 +280,21 @@ class Engine:
     def clear_duplicate_flag(self):
         """ClearDuplicateFlag: FLAG &^= 0x400 on every staged record (elp_clear_duplicate_flag)"""
         self._check(self.L.elp_clear_duplicate_flag(self.h))
+
+    def replace_reference_dictionary(self, new_of_old, ref_len_new) -> int:
+        """--replace-reference-sequences on the staged records (elp_replace_reference_dictionary): new_of_old[r] = index of old contig r's
+        name in the new dictionary or -1 (dictionary_map), ref_len_new = the new @SQ LN values -> number of records rejected by this call.
+        References and known sites are set AFTER the call, under the new refids."""
+        m = np.ascontiguousarray(new_of_old, dtype=np.int32).reshape(-1)
+        ln = np.ascontiguousarray(ref_len_new, dtype=np.int32).reshape(-1)
+        n_ref = getattr(self, "_n_ref_now", None)
+        n_ref = self.header.n_ref if n_ref is None else n_ref
+        if m.size != n_ref:  # (the library reads new_of_old[0 .. n_ref) of the dictionary in force)
+            raise ElpError(-1, "replace_reference_dictionary: new_of_old has %d entries, the context's dictionary %d contigs" % (m.size, n_ref))
+        n = C.c_uint64()
+        self._check(self.L.elp_replace_reference_dictionary(self.h, _vp(m), int(ln.size), _vp(ln), C.byref(n)))
+        self._n_ref_now = int(ln.size)  # until reset() / a new header
+        return int(n.value)
 
     def copy_records_from(self, src: "Engine", idx: np.ndarray, new_split: Optional[int] = None, tag_sr=False):
         """appends src's records idx (staging indices) to this context, device to device (elp_copy_records).  tag_sr: False / True (all
@@ -544,6 +560,26 @@ class Engine:
             self._check(self.L.elp_profile_get(self.h, i, C.byref(name), C.byref(cnt), C.byref(ms)))
             out[name.value.decode()] = (int(cnt.value), float(ms.value))
         return out
+
+
+def _flat_names(names):
+    enc = [s.encode() if isinstance(s, str) else bytes(s) for s in names]
+    cat = np.frombuffer(b"".join(enc) + b"\0", dtype=np.uint8)
+    off = np.cumsum([0] + [len(e) for e in enc]).astype(np.uint32)
+    return cat, off, len(enc)
+
+
+def dictionary_map(old_names: Sequence, new_names: Sequence) -> Tuple[np.ndarray, bool]:
+    """elp_host_dictionary_map: the @SQ names (str or bytes) of the input's and of the new dictionary -> (new_of_old int32 [len(old_names)],
+    order_kept).  order_kept False means: if the input's @HD SO is `coordinate`, the output's is `unknown` (filters/simple-filters.go:36-51)"""
+    oc, oo, n_old = _flat_names(old_names)
+    nc, no, n_new = _flat_names(new_names)
+    out = np.full(n_old, -2, dtype=np.int32)
+    kept = C.c_int(-1)
+    rc = _lib.host().elp_host_dictionary_map(_vp(oc), _vp(oo), n_old, _vp(nc), _vp(no), n_new, _vp(out), C.byref(kept))
+    if rc != 0:
+        raise ValueError("elp_host_dictionary_map: %d" % rc)
+    return out, bool(kept.value)
 
 
 def group_unique_id() -> bytes:

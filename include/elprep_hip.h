@@ -207,6 +207,43 @@ int elp_set_tag_filter(elp_ctx *ctx, const uint8_t *remove_keys, int n_remove, c
 int elp_set_replace_read_group(elp_ctx *ctx, const uint8_t *id, int id_len);
 int elp_filter_exact_strict(elp_ctx *ctx, uint64_t *n_rejected_out /* may be NULL */);
 int elp_clear_duplicate_flag(elp_ctx *ctx);
+/* elp_replace_reference_dictionary: `--replace-reference-sequences` (ReplaceReferenceSequenceDictionary, filters/simple-filters.go:32-60,
+ *   appended to filters1 at cmd/filter.go:752-755, cmd/sfm.go:423-425) together with the renumbering that AddREFID makes behind it under
+ *   the new header.SQ (:208-231, cmd/filter.go:762-766).  Staged records carry the OLD file's refids, in their bytes and in the REFID /
+ *   RNEXT columns; the sort keys, the duplicate-marking keys, the BQSR reference look-ups, the contig order of the output and the refID /
+ *   next_refID the BAM writer emits (sam/bam-files.go:642-647, 674-681) all follow the NEW dictionary.
+ *   new_of_old[r] (r < the context's n_ref) = index in the new dictionary of old contig r's name, -1 if the new dictionary does not hold
+ *   it (elp_host_dictionary_map, elprep_host.h, makes it from the names); ref_len_new[n_ref_new] = the new @SQ LN values.
+ *   Records: one stays iff its refid < 0 (RNAME `*`: dictTable["*"], :53) or new_of_old[refid] >= 0 (:58); every other record gets the
+ *   state elp_filter_records gives (same effect on everything that follows).  The counts of the calls add up as for
+ *   elp_filter_exact_strict: a record that was live is counted in *n_rejected_out (and leaves elp_num_sorted()); an sr-tagged copy that
+ *   is rejected was counted when it was staged; a record an earlier call rejected is not looked at again.
+ *   Columns, for EVERY record whatever its state: refid = refid < 0 ? -1 : new_of_old[refid], next_refid likewise (a kept record whose
+ *   mate's contig left the dictionary gets next_refid -1, as the writer emits for a name it does not hold; `=` needs no case of its own,
+ *   the column holds it resolved; a value the old dictionary does not hold - possible in RNEXT of staged BAM bytes - names nothing: -1).
+ *   A write that would change nothing is not made: the identity map with n_ref_new == n_ref leaves every column byte as it was.
+ *   Header state: the context's reference table becomes the new one - elp_bqsr_set_reference / elp_bqsr_set_known_sites made BEFORE the
+ *   call are dropped (their refids were the old ones'): the host sets them afterwards under the new refids.  Everything called afterwards
+ *   sees the new dictionary.  The emitters take refID / next_refID from the columns, so the output records carry the new ones.
+ *   Call order: where the reference's filter stands - behind elp_filter_records, elp_filter_exact_strict and elp_clean_sam, in front of
+ *   elp_mark_duplicates (elp_clear_duplicate_flag, :729-731, may stand on either side: the two touch different columns).  CleanSam
+ *   precedes it in filters1 (cmd/filter.go:747-749 against :752-755) and so
+ *   clips against the OLD dictionary's LN: call elp_clean_sam first.  A second call on the same records is allowed; it maps from the
+ *   dictionary as it then is.
+ *   Errors: ELP_ERR_ARG without a header, for n_ref_new < 0, a NULL array that is needed, or a new_of_old[r] outside [-1, n_ref_new) -
+ *   all checked on the host before anything is launched or changed (a call refused so changes nothing; after a HIP failure inside the
+ *   call the context is good for elp_reset / elp_set_header only).
+ *   Afterwards the staged bytes and the header no longer agree: elp_stage, elp_stage_columns, elp_stage_bam and elp_stage_bgzf return
+ *   ELP_ERR_ARG until elp_reset or elp_set_header.  elp_reset returns to the dictionary elp_set_header gave (references and known sites
+ *   set under the new refids are dropped with it, and elp_set_header behind a replacement drops them likewise), so a host that resets and stages the next file of the same header goes on as before.
+ *   elp_copy_records, elp_exchange_records and elp_emit_merged_bam return ELP_ERR_ARG between two contexts of which one has replaced its
+ *   dictionary and the other has not (the rule of elp_set_replace_read_group); two that both did, with equal results, pass.
+ *   The sort keys (with key passes made ahead, elp_sort_ahead), scores, marks, any permutation and a snapshot (elp_rollback cannot
+ *   restore refids) become invalid (csrc/derived.hpp: dictionary_replaced).  The @SQ lines and @HD SO of the output stay with the host.
+ *   Reads: the REFID, RNEXT and record-state columns (9 bytes per record), the map (from LDS up to 256 old contigs, else from HBM).
+ *   Writes: the same three columns where a value changes; the context's reference table.  n_rejected_out may be NULL. */
+int elp_replace_reference_dictionary(elp_ctx *ctx, const int32_t *new_of_old /* [old n_ref] */, int32_t n_ref_new,
+                                     const int32_t *ref_len_new /* [n_ref_new] */, uint64_t *n_rejected_out /* may be NULL */);
 
 /* ---- fused per-record predicates: filters/simple-filters.go ----
  * The filters that stand in front of MarkDuplicates in filters1 (cmd/filter.go:696-803), evaluated in one pass over the staged

@@ -60,6 +60,22 @@ char *elp_dup_metrics_report(const int64_t *counters, int n_lib, const char *con
 char *elp_dup_metrics_report_hist(const int64_t *counters, const int64_t *hist, int hist_len, int n_lib, const char *const *lib_names,
                                   const char *command_line);
 
+/* The host half of `--replace-reference-sequences` (ReplaceReferenceSequenceDictionary, filters/simple-filters.go:32-60): the @SQ SN
+ * names of the input's dictionary and of the new one -> what elp_replace_reference_dictionary (elprep_hip.h) takes.  The names lie behind
+ * each other, off[k] .. off[k + 1] = the bytes of name k (n + 1 offsets: the form of elp_set_read_group_ids_flat).
+ *   new_of_old[r]    index of old contig r's name in the new dictionary, -1 if it does not hold it.  This is AddREFID's table under the new
+ *                    header (:208-231): a name the new dictionary holds more than once gets its LAST index (the map assignment of
+ *                    :211-213 overwrites).  Two old contigs of one name both map.
+ *   *order_kept_out  (may be NULL) the verdict of :36-51 on the sorting order: walk the new entries in order, pos = the FIRST old index of
+ *                    the same name (utils.Find); entries that are not found are skipped; the first found pos that is not greater than the
+ *                    previous found one gives 0 and ends the walk (header.SetHDSO(sam.Unknown); break), otherwise 1.  The reference makes
+ *                    this test only if the input's @HD SO is `coordinate` (:36): the host applies a 0 - SO becomes `unknown` - only then,
+ *                    and leaves any other SO as it is.
+ * The @SQ lines of the output header are the new dictionary's (header.SQ = dict, :57); they and SO stay with the host.
+ * Returns 0, or -1 for negative counts, a NULL array that is needed, or offsets that decrease. */
+int elp_host_dictionary_map(const uint8_t *old_names, const uint32_t *old_off, int32_t n_old, const uint8_t *new_names, const uint32_t *new_off,
+                            int32_t n_new, int32_t *new_of_old /* [n_old] */, int *order_kept_out);
+
 #ifdef __cplusplus
 }
 #endif
