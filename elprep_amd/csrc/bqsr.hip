@@ -724,6 +724,7 @@ struct CountBody {
   // (with four read groups and six qualities the tables take 50 KB); 256 KiB steps save the per-step restart of the pipeline.
   // NTV = 1024: one workgroup per CU shares one big table (many qualities x read groups): same waves per SIMD as two of 512
   static constexpr int NT = NTV, TILES = 8, RMAX = NTV == 1024 ? 512 : 256;
+  static constexpr bool TILE_ENDS = true;  // the private table is flushed at the end of an index tile, not of a step (tile_end)
   // kernel arguments (scalar copies: a reference to the argument struct would keep this object in scratch memory)
   const uint64_t *__restrict__ seq_off;
   const uint8_t *__restrict__ qual;
@@ -1020,7 +1021,12 @@ struct CountBody {
     __syncthreads();
   }
   // a cycle cell (16 | 16 bits) takes at most one count per read, a context cell (32 | 32 bits) at most one per base; a tile
-  // starts at most FL_TILE reads and holds at most FL_TILE + FL_MAX_READ bases
+  // starts at most FL_TILE reads and holds at most FL_TILE + FL_MAX_READ bases.  The table is flushed at the end of the first index
+  // tile behind which more than 30000 reads have started since the last flush: a cycle cell holds at most 30000 + FL_TILE = 62768.
+  // (flat_run ends a span of tiles where tile_due says so - a step of eight tiles of one-base reads starts 262144 reads.)
+  __device__ __forceinline__ bool tile_due(uint32_t nreads, uint64_t nbases) const {
+    return reads_since_flush + nreads > 30000u || bases_since_flush + nbases > (1ull << 31);
+  }
   __device__ __forceinline__ void tile_end(uint32_t nreads, uint64_t nbases) {
     reads_since_flush += nreads;
     bases_since_flush += nbases;
@@ -1138,6 +1144,7 @@ template <bool CHECK_CYCLE, int MODE>
 struct ApplyBody {
   // 128 KiB steps in groups of up to 512 reads (12 B of LDS per read)
   static constexpr int NT = FL_THREADS, TILES = 4, RMAX = 512;
+  static constexpr bool TILE_ENDS = false;
   static constexpr int ES = MODE == 1 ? 1 : 2;  // bytes per level-1 entry
   const uint64_t *__restrict__ seq_off;
   const uint64_t *__restrict__ qual_off;

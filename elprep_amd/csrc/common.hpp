@@ -265,6 +265,8 @@ struct elp_ctx {
     int bgzf_stored = 0;       // 1: elp_emit_sorted_bgzf writes stored DEFLATE blocks (round 4's form) instead of compressing
     int apply_wgs = 0;         // 1 .. 3: workgroups per CU of the one-length ApplyBQSR kernel (default: as many as its LDS allows, at most 3) - A/B runs
                                // of a step whose sort runs at the same time and needs LDS of its own
+    int count3_grid = 0;       // > 0: the one-length count kernel runs min(this, CUs) workgroups (default: one per CU) - tests reach the in-loop
+                               // flush of its private table with a few hundred thousand reads instead of millions
     int presort_tile = 0;      // elp_sort_ahead: radix tile of the key passes made ahead (1 / 2 / 3 = 4096 / 8192 / 16384 keys; default 2: a tile of
                                // 16384 keys is a 1024-thread workgroup around 128 KB of LDS, which finds no CU while kernels of small workgroups
                                // keep every CU partly occupied)

@@ -512,8 +512,9 @@ int count3_plan(int n_cov, int n_q, int lmax, int *rsw_out, int *rlog_out, size_
 }
 
 int count3_launch(elp_ctx *c, const Count3Args &A, const QMap &qm, size_t dyn) {
-  // one workgroup per CU; they share the launch's trips evenly
-  const int grid = c->n_cu;
+  // one workgroup per CU; they share the launch's trips evenly (elp_set_tuning "count3_grid": fewer of them, so that a small read set
+  // gives a workgroup as many trips as a large one does)
+  const int grid = c->tune.count3_grid > 0 ? std::min(c->tune.count3_grid, c->n_cu) : c->n_cu;
 #define ELP_C3K(RL, OT)                                                                                                                          \
   do {                                                                                                                                           \
     ELP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bqsr_count3<RL, OT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \

@@ -155,6 +155,11 @@ struct Chunk {
 //                                                             would sit in the same in-order counter (vmcnt) and be waited for, with
 //                                                             its full latency, as soon as the loaded registers are needed
 //   void group_end(uint32_t g0, uint32_t ng)                  all threads, after a barrier
+//   static constexpr bool TILE_ENDS                           false: tile_end is called once per step, with the step's reads.  true:
+//                                                             the step is walked in spans of whole index tiles - a span ends with the
+//                                                             first tile at whose end tile_due says so (or with the step), groups do
+//                                                             not cross a span's end and tile_end is called there with the span's reads
+//   bool tile_due(uint32_t nreads, uint64_t nbases)           (TILE_ENDS) uniform: has tile_end something to do after this many more reads?
 //   void tile_end(uint32_t nreads, uint64_t nbases)           all threads (uniform), may contain barriers
 // The lane's next block is prefetched before the current one is processed, so the HBM latency of block i+1 hides behind the ALU
 // and LDS work of block i (the loads stay in flight across the loop's back edge).
@@ -167,99 +172,109 @@ __device__ __forceinline__ void flat_run(const uint64_t *__restrict__ qual_off, 
   const uint64_t ntiles = (qual_bytes + FL_TILE - 1) / FL_TILE, nsteps = (ntiles + Body::TILES - 1) / Body::TILES;
   for (uint64_t t = blockIdx.x; t < nsteps; t += gridDim.x) {
     const uint64_t t1 = (t + 1) * Body::TILES < ntiles ? (t + 1) * Body::TILES : ntiles;
-    const uint32_t r_first = tile_first[t * Body::TILES], r_end = tile_first[t1];
-    for (uint32_t g0 = r_first; g0 < r_end; g0 += RMAX) {
-      const uint32_t ng = (r_end - g0 < RMAX) ? r_end - g0 : RMAX;  // reads [g0, g0 + ng)
-      const uint64_t base = qual_off[g0];
-      const uint32_t len0 = (uint32_t)(qual_off[g0 + 1] - base);
-      int same = 1;  // every read of the group has len0 bases (what a sequencer writes): slots are found by arithmetic alone
-      for (uint32_t k = threadIdx.x; k <= ng; k += Body::NT) {
-        const uint32_t o = (uint32_t)(qual_off[g0 + k] - base);
-        L.off[k] = o;
-        same &= o == k * len0;
+    for (uint64_t tl = t * Body::TILES, tm; tl < t1; tl = tm) {
+      // the span of tiles [tl, tm): the whole step, unless the body has work at a tile's end inside it (one test per step then:
+      // a step of ordinary reads loads nothing else)
+      tm = t1;
+      const uint32_t r_first = tile_first[tl];
+      if constexpr (Body::TILE_ENDS) {
+        if (B.tile_due(tile_first[t1] - r_first, qual_off[tile_first[t1]] - qual_off[r_first]))
+          for (tm = tl + 1; tm < t1 && !B.tile_due(tile_first[tm] - r_first, qual_off[tile_first[tm]] - qual_off[r_first]); tm++) {}
       }
-      B.stage(g0, ng);
-      const bool uniform = __syncthreads_and(same) != 0 && len0 != 0;
-      const uint32_t nslots = (L.off[ng] + 15u * ng) >> 4;  // slot of read k: (off[k] + 15 k) >> 4
-      B.slots(nslots);
-      const float inv_avg = nslots ? (float)ng / (float)nslots : 0.f, inv_step = 1.0f / (float)(len0 + 15u);
-      // Uniform groups: slot s belongs to read k = (16 s + 15) / step (step = len0 + 15: read k starts at slot (step k) >> 4), and with
-      // r = (16 s + 15) % step the block starts at base r & ~15 of the read.  A lane's slots are NT apart, so (k, r) of its next
-      // slot follow from the current ones by adding the (uniform) quotient and remainder of 16 NT / step - a handful of VALU
-      // instructions per block instead of a division.
-      const uint32_t step = len0 + 15u;  // < 2^24, like every read index: 24-bit multiplies
-      uint32_t uk = 0, ur = 0, udk = 0, udr = 0;
-      if (uniform) {
-        udk = (16u * Body::NT) / step;
-        udr = (16u * Body::NT) - udk * step;
-        const uint32_t q = 16u * threadIdx.x + 15u;  // < 2^24: the float quotient is off by at most one
-        int k = (int)((float)q * inv_step);
-        k = (uint32_t)k * step > q ? k - 1 : k;
-        k = ((uint32_t)k + 1u) * step <= q ? k + 1 : k;
-        uk = (uint32_t)k;
-        ur = q - uk * step;
-      }
-      // locate slot s and issue its loads (the uniform path must be called for s = threadIdx.x, then s + NT, s + 2 NT, ... in turn)
-      auto fetch = [&](uint32_t s, typename Body::Pre &pre) __attribute__((always_inline)) -> bool {
+      const uint32_t r_end = tile_first[tm];
+      for (uint32_t g0 = r_first; g0 < r_end; g0 += RMAX) {
+        const uint32_t ng = (r_end - g0 < RMAX) ? r_end - g0 : RMAX;  // reads [g0, g0 + ng)
+        const uint64_t base = qual_off[g0];
+        const uint32_t len0 = (uint32_t)(qual_off[g0 + 1] - base);
+        int same = 1;  // every read of the group has len0 bases (what a sequencer writes): slots are found by arithmetic alone
+        for (uint32_t k = threadIdx.x; k <= ng; k += Body::NT) {
+          const uint32_t o = (uint32_t)(qual_off[g0 + k] - base);
+          L.off[k] = o;
+          same &= o == k * len0;
+        }
+        B.stage(g0, ng);
+        const bool uniform = __syncthreads_and(same) != 0 && len0 != 0;
+        const uint32_t nslots = (L.off[ng] + 15u * ng) >> 4;  // slot of read k: (off[k] + 15 k) >> 4
+        B.slots(nslots);
+        const float inv_avg = nslots ? (float)ng / (float)nslots : 0.f, inv_step = 1.0f / (float)(len0 + 15u);
+        // Uniform groups: slot s belongs to read k = (16 s + 15) / step (step = len0 + 15: read k starts at slot (step k) >> 4), and with
+        // r = (16 s + 15) % step the block starts at base r & ~15 of the read.  A lane's slots are NT apart, so (k, r) of its next
+        // slot follow from the current ones by adding the (uniform) quotient and remainder of 16 NT / step - a handful of VALU
+        // instructions per block instead of a division.
+        const uint32_t step = len0 + 15u;  // < 2^24, like every read index: 24-bit multiplies
+        uint32_t uk = 0, ur = 0, udk = 0, udr = 0;
         if (uniform) {
-          const uint32_t k = uk, k0 = ur & ~15u;
-          // state of the lane's next slot
-          ur += udr;
-          const bool wrap = ur >= step;
-          uk += udk + (wrap ? 1u : 0u);
-          ur = wrap ? ur - step : ur;
-          if (k0 >= len0) return false;  // the (at most one) empty slot behind a read
-          const uint32_t nb = len0 - k0 < 16u ? len0 - k0 : 16u;
-          return B.prefetch(k, (int)k0, (int)nb, base + __umul24(len0, k) + k0, s, pre);
+          udk = (16u * Body::NT) / step;
+          udr = (16u * Body::NT) - udk * step;
+          const uint32_t q = 16u * threadIdx.x + 15u;  // < 2^24: the float quotient is off by at most one
+          int k = (int)((float)q * inv_step);
+          k = (uint32_t)k * step > q ? k - 1 : k;
+          k = ((uint32_t)k + 1u) * step <= q ? k + 1 : k;
+          uk = (uint32_t)k;
+          ur = q - uk * step;
         }
-        // read owning slot s: guess g from the mean; the four offsets around g are read at once (one LDS latency) and decide
-        // among g-1, g, g+1; otherwise walk
-        int k = (int)((float)s * inv_avg);
-        k = k >= (int)ng - 1 ? (int)ng - 2 : k;
-        k = k < 1 ? 1 : k;
-        // straight-line on purpose (bitwise &, selects): with && the compiler nests branches and reads the offsets in two
-        // dependent LDS round trips.  For ng < 3 the four words are read all the same (the array is longer) and not used.
-        const uint32_t a0 = L.off[k - 1], a1 = L.off[k], a2 = L.off[k + 1], a3 = L.off[k + 2];
-        const uint32_t v0 = (a0 + 15u * (uint32_t)(k - 1)) >> 4, v1 = (a1 + 15u * (uint32_t)k) >> 4, v2 = (a2 + 15u * (uint32_t)(k + 1)) >> 4,
-                       v3 = (a3 + 15u * (uint32_t)(k + 2)) >> 4;
-        const bool found = (ng >= 3u) & (s >= v0) & (s < v3);
-        const bool hi = s >= v2, mid = s >= v1;
-        uint32_t o = hi ? a2 : (mid ? a1 : a0);
-        uint32_t nxt = hi ? a3 : (mid ? a2 : a1);
-        k = found ? (hi ? k + 1 : (mid ? k : k - 1)) : k;
-        if (!found) {
-          k = k >= (int)ng ? (int)ng - 1 : k;
-          while (((L.off[k] + 15u * (uint32_t)k) >> 4) > s) k--;
-          while (((L.off[k + 1] + 15u * (uint32_t)(k + 1)) >> 4) <= s) k++;
-          o = L.off[k];
-          nxt = L.off[k + 1];
+        // locate slot s and issue its loads (the uniform path must be called for s = threadIdx.x, then s + NT, s + 2 NT, ... in turn)
+        auto fetch = [&](uint32_t s, typename Body::Pre &pre) __attribute__((always_inline)) -> bool {
+          if (uniform) {
+            const uint32_t k = uk, k0 = ur & ~15u;
+            // state of the lane's next slot
+            ur += udr;
+            const bool wrap = ur >= step;
+            uk += udk + (wrap ? 1u : 0u);
+            ur = wrap ? ur - step : ur;
+            if (k0 >= len0) return false;  // the (at most one) empty slot behind a read
+            const uint32_t nb = len0 - k0 < 16u ? len0 - k0 : 16u;
+            return B.prefetch(k, (int)k0, (int)nb, base + __umul24(len0, k) + k0, s, pre);
+          }
+          // read owning slot s: guess g from the mean; the four offsets around g are read at once (one LDS latency) and decide
+          // among g-1, g, g+1; otherwise walk
+          int k = (int)((float)s * inv_avg);
+          k = k >= (int)ng - 1 ? (int)ng - 2 : k;
+          k = k < 1 ? 1 : k;
+          // straight-line on purpose (bitwise &, selects): with && the compiler nests branches and reads the offsets in two
+          // dependent LDS round trips.  For ng < 3 the four words are read all the same (the array is longer) and not used.
+          const uint32_t a0 = L.off[k - 1], a1 = L.off[k], a2 = L.off[k + 1], a3 = L.off[k + 2];
+          const uint32_t v0 = (a0 + 15u * (uint32_t)(k - 1)) >> 4, v1 = (a1 + 15u * (uint32_t)k) >> 4, v2 = (a2 + 15u * (uint32_t)(k + 1)) >> 4,
+                         v3 = (a3 + 15u * (uint32_t)(k + 2)) >> 4;
+          const bool found = (ng >= 3u) & (s >= v0) & (s < v3);
+          const bool hi = s >= v2, mid = s >= v1;
+          uint32_t o = hi ? a2 : (mid ? a1 : a0);
+          uint32_t nxt = hi ? a3 : (mid ? a2 : a1);
+          k = found ? (hi ? k + 1 : (mid ? k : k - 1)) : k;
+          if (!found) {
+            k = k >= (int)ng ? (int)ng - 1 : k;
+            while (((L.off[k] + 15u * (uint32_t)k) >> 4) > s) k--;
+            while (((L.off[k + 1] + 15u * (uint32_t)(k + 1)) >> 4) <= s) k++;
+            o = L.off[k];
+            nxt = L.off[k + 1];
+          }
+          const uint32_t len = nxt - o;
+          const uint32_t k0 = (s - ((o + 15u * (uint32_t)k) >> 4)) << 4;
+          if (k0 >= len) return false;  // the (at most one) empty slot behind a read
+          const uint32_t nb = len - k0 < 16u ? len - k0 : 16u;
+          return B.prefetch((uint32_t)k, (int)k0, (int)nb, base + o + k0, s, pre);
+        };
+        uint32_t s = threadIdx.x;
+        typename Body::Pre cur;
+        bool have = s < nslots ? fetch(s, cur) : false;
+  #pragma unroll 1
+        while (s < nslots) {
+          B.retire();
+          const uint32_t sn = s + Body::NT;
+          typename Body::Pre nxt;
+          const bool have_n = sn < nslots ? fetch(sn, nxt) : false;
+          if (have) B.process(cur);
+          cur = nxt;
+          have = have_n;
+          s = sn;
         }
-        const uint32_t len = nxt - o;
-        const uint32_t k0 = (s - ((o + 15u * (uint32_t)k) >> 4)) << 4;
-        if (k0 >= len) return false;  // the (at most one) empty slot behind a read
-        const uint32_t nb = len - k0 < 16u ? len - k0 : 16u;
-        return B.prefetch((uint32_t)k, (int)k0, (int)nb, base + o + k0, s, pre);
-      };
-      uint32_t s = threadIdx.x;
-      typename Body::Pre cur;
-      bool have = s < nslots ? fetch(s, cur) : false;
-#pragma unroll 1
-      while (s < nslots) {
         B.retire();
-        const uint32_t sn = s + Body::NT;
-        typename Body::Pre nxt;
-        const bool have_n = sn < nslots ? fetch(sn, nxt) : false;
-        if (have) B.process(cur);
-        cur = nxt;
-        have = have_n;
-        s = sn;
+        __syncthreads();
+        B.group_end(g0, ng);
+        __syncthreads();
       }
-      B.retire();
-      __syncthreads();
-      B.group_end(g0, ng);
-      __syncthreads();
+      B.tile_end(r_end - r_first, qual_off[r_end] - qual_off[r_first]);
     }
-    B.tile_end(r_end - r_first, qual_off[r_end] - qual_off[r_first]);
   }
 }
 

@@ -75,6 +75,7 @@ __device__ __forceinline__ uint32_t first_bytes32(int n) { return n <= 0 ? 0u : 
 // any quality > 93 in a candidate is an error.  SWAR over the lane's 16 bytes, v_sad_u8 for the byte sums.
 struct ScoreBody {
   static constexpr int NT = FL_THREADS, TILES = 4, RMAX = 1024;
+  static constexpr bool TILE_ENDS = false;
   const uint16_t *__restrict__ flag;
   const uint8_t *__restrict__ qual;
   int32_t *score;

@@ -50,6 +50,8 @@ int elp_rollback(elp_ctx *ctx);
  *   "bgzf_weak_guess"  1: elp_stage_bgzf's blocks guess their first record start blindly (every guess is then repaired: same result)
  *   "score_kernel"     1: general Phred-score / low-quality-tail kernel even for read sets of one length
  *   "count3_rlog"      >= 0: log2 of the context-cell replication of the one-length count kernel (measurements)
+ *   "count3_grid"      v > 0: the one-length count kernel runs min(v, CUs) workgroups instead of one per CU (tests: one workgroup takes every
+ *                      trip, so its private table reaches its in-loop flushes on a small read set); negative values are refused
  *   "qual_hint"        1: no sampled quality hint (the gather sizes its tables on the report-and-retry path)
  *   "qual_hint_drop"   q >= 0: quality q is removed from the sampled hint (the kernels' no-slot paths)
  *   "pair_table_slots" cap on the LDS table slots per pair bucket of elp_mark_duplicates (a power of two >= 2; 0 = no cap): a
