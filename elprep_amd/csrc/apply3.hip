@@ -2,7 +2,7 @@
 //
 // Reference: BaseRecalibratorTables.ApplyBQSR (filters/bqsr.go:936-1005): every base with quality >= 6 of a record whose read group is
 // in the tables is replaced by the memo value of (read group, quality, cycle, context); cycle and context are taken on the full,
-// unclipped read.  Same bytes as k_bqsr_apply_flat (bqsr.hip), which stays as the general kernel (ragged lengths, reads longer than
+// unclipped read.  Same bytes as k_bqsr_apply_flat (bqsr_apply.hip), which stays as the general kernel (ragged lengths, reads longer than
 // --max-cycle, LUTs with more than ~250 distinct rows).
 //
 //   - A workgroup trip covers RPI = 1024 / (blocks per read) whole reads; lane t is block t % bpr of read slot t / bpr for the whole
@@ -27,7 +27,7 @@
 namespace elp {
 
 constexpr uint32_t A3_N1 = 0x11111111u, A3_C3 = 0x33333333u;
-constexpr int A3_ROW = 20;  // bytes between two level-2 rows in LDS (17 used)
+// (A3_ROW, the bytes between two level-2 rows in LDS: bqsr_plan.hpp)
 constexpr int A3_NT = 512;  // three workgroups per CU around three copies of the LUT (~50 KB each): six waves per SIMD
 __global__ __launch_bounds__(256) void k_apply_records(uint64_t n, uint32_t len, int lmax, const uint16_t *__restrict__ flag, const uint16_t *__restrict__ rgid,
                                                        const uint16_t *__restrict__ rg_cov, const uint64_t *__restrict__ qbounds,
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void k_apply_records(uint64_t n, uint32_t len,
 
 // Round 5 - the records SPLIT BY COVARIATE (many read groups: the level-1 tables of all covariates do not fit one workgroup's LDS, or the
 // LUT has more distinct rows than one-byte ids hold): only the reads ApplyBQSR touches get a record, the records of one covariate lie
-// together (counts per covariate, offsets, a scatter: the shape of k_c3_other_* in bqsr.hip), the read's staging index next to the
+// together (counts per covariate, offsets, a scatter: the shape of k_c3_other_* in bqsr_count.hip), the read's staging index next to the
 // record; a workgroup of k_bqsr_apply3<true> then holds ONE covariate's level 1 and that covariate's own row dictionary at a time.
 constexpr int A3_MAXCOV = 256, A3_RTILE = 1024;
 __device__ __forceinline__ int apply_read_cov(uint16_t rg, const uint16_t *__restrict__ rg_cov, const uint8_t *__restrict__ cov_present, uint32_t *err) {
@@ -262,6 +262,14 @@ struct Apply3 {
   }
 };
 
+// The static LDS apply3_bytes (bqsr_plan.hpp) and apply3_launch set aside for k_bqsr_apply3: the kernel's __shared__ arrays, term by term (the
+// kernel asserts the sums against its own declarations), and a margin.  The covariate split's prefix-sum arrays come on top in its launch only.
+constexpr size_t APPLY3_LDS_ARRAYS = sizeof(uint8_t[A3_MAXCOV]);
+constexpr size_t APPLY3_LDS_ARRAYS_SPLIT = sizeof(uint32_t[A3_MAXCOV]) + sizeof(uint32_t[A3_MAXCOV + 1]) + sizeof(uint32_t[4]);
+constexpr size_t APPLY3_LDS = APPLY3_LDS_ARRAYS + 256, APPLY3_LDS_SPLIT = APPLY3_LDS_ARRAYS_SPLIT + 236;
+extern const size_t APPLY3_STATIC_LDS = APPLY3_LDS;
+static_assert(APPLY3_LDS == 512 && APPLY3_LDS_SPLIT == 2304, "the budgets the plan was written around");
+
 template <bool SPLIT>
 __global__ __launch_bounds__(A3_NT, 6) void k_bqsr_apply3(Apply3Args A) {  // six waves per SIMD = three workgroups per CU: <= 80 vector registers
   extern __shared__ __attribute__((aligned(16))) uint8_t llut[];
@@ -297,6 +305,7 @@ __global__ __launch_bounds__(A3_NT, 6) void k_bqsr_apply3(Apply3Args A) {  // si
     }
   };
   __shared__ uint8_t s_present[A3_MAXCOV];
+  static_assert(sizeof(s_present) == APPLY3_LDS_ARRAYS, "APPLY3_LDS_ARRAYS lists the kernel's __shared__ arrays: add a new one there too");
   if (!SPLIT) {
     fill(0, A.n_cov, (int)*A.n_dict, A.t2);
     if (A.cov_present)
@@ -413,6 +422,7 @@ __global__ __launch_bounds__(A3_NT, 6) void k_bqsr_apply3(Apply3Args A) {  // si
   } else {
     // trips per covariate, their exclusive prefix sums (s_pre[k] for k >= n_cov = the total)
     __shared__ uint32_t s_cnt[A3_MAXCOV], s_pre[A3_MAXCOV + 1], s_wsum[4];
+    static_assert(sizeof(s_cnt) + sizeof(s_pre) + sizeof(s_wsum) == APPLY3_LDS_ARRAYS_SPLIT, "APPLY3_LDS_ARRAYS_SPLIT lists these arrays: add a new one there too");
     {
       const uint32_t my_cnt = (int)threadIdx.x < A.n_cov ? A.cov_cnt[threadIdx.x] : 0u;
       const uint32_t my_trips = (my_cnt + RPI - 1u) / RPI;
@@ -462,14 +472,6 @@ __global__ __launch_bounds__(A3_NT, 6) void k_bqsr_apply3(Apply3Args A) {  // si
   }
 }
 
-// LDS of a launch: level 1 + room for 256 level-2 rows (their number is not read back in front of the launch); 1 = does not fit
-int apply3_bytes(int n_cov, int n_qi, int lmax, size_t *dyn_out) {
-  const size_t n1 = (size_t)n_cov * (size_t)(6 + n_qi + 1) * (size_t)(2 * lmax + 1);
-  const size_t dyn = ((n1 + 15) & ~(size_t)15) + (size_t)256 * A3_ROW + 16;
-  *dyn_out = dyn;
-  return dyn + 512 <= 160 * 1024 ? 0 : 1;
-}
-
 int apply3_launch(elp_ctx *c, int max_cycle, const uint8_t *d_lut, const uint8_t *d_cov_present, const uint16_t *t1, const uint8_t *t2, const uint32_t *n_dict_dev,
                   int n_qi, int lmax, size_t dyn, bool split) {
   const uint64_t n = c->n;
@@ -481,7 +483,7 @@ int apply3_launch(elp_ctx *c, int max_cycle, const uint8_t *d_lut, const uint8_t
     for (uint32_t slot = 0; slot < A3_NT / bpr; slot++)
       if (((slot * bpr + bpr - 1u) & 63u) == 0) group = 64;
   const uint32_t rpi = (group / bpr) * (A3_NT / group);
-  unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(3, (160 * 1024) / (dyn + 512 + (split ? 2304 : 0))));
+  unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(3, LDS_CU / (dyn + APPLY3_LDS + (split ? APPLY3_LDS_SPLIT : 0))));
   if (c->tune.apply_wgs >= 1 && c->tune.apply_wgs <= 3) per_cu = std::min(per_cu, (unsigned)c->tune.apply_wgs);
   const int grid = (int)std::min<uint64_t>((n + rpi - 1) / rpi, (uint64_t)c->n_cu * per_cu);
   uint2 *recs;

@@ -1,8 +1,10 @@
 // bqsr_common.hpp — what the BQSR translation units share: the per-record descriptor the prologue kernels leave for the count
-// kernels, the 4-bit packed reference windows, LDS atomics and the one-instruction helpers.  (Moved out of bqsr.hip in round 3, when
-// the second count kernel - count2.hip - arrived.)
+// kernels, the 4-bit packed reference windows, LDS atomics and the one-instruction helpers, and the functions by which the stage's
+// translation units call each other: bqsr.hip (reference, known sites, the gather's host side, table fetches) -> bqsr_prologue.hip,
+// bqsr_count.hip, count3.hip; bqsr_apply.hip -> apply3.hip.  The launch plans are host arithmetic of their own (bqsr_plan.hpp).
 #pragma once
 #include "bqsr_dev.hpp"
+#include "bqsr_plan.hpp"
 #include "flat.hpp"
 
 namespace elp {
@@ -166,9 +168,7 @@ enum : uint32_t { RC_REV = 1u << 8, RC_PAR = 1u << 9, RC_NEG = 1u << 10, RC_MULT
 // (k_c3_seg_hist: the prologue's wave -> segment mapping applied to the RGID column), so the class-1 area is n records whatever the
 // number of read groups - the fixed stride had to hold the worst case per segment, ncs * n records in all: 100 GB for 64 read groups and
 // 50 M reads.  nseg = max(64, ncs): up to 256 segments, i.e. any number of read-group covariates a u8 holds.
-constexpr int C3_NSEG = 64;       // segments without the covariate split; the least with it
-constexpr int C3_MAXSEG = 256;
-constexpr int C3_CSTRIDE = 64;  // words between two counters: every counter in a 256-byte line of its own (one line = one L2 channel would serialise them all)
+// (C3_NSEG, C3_MAXSEG, C3_CSTRIDE: bqsr_plan.hpp)
 struct RecOut {
   BqRec *recs;     // nullptr: descriptors are written instead (general count kernel)
   uint32_t *cnt;   // [s * C3_CSTRIDE], s < nseg: records in segment s; [nseg * C3_CSTRIDE]: records in the "other" region
@@ -179,9 +179,6 @@ struct RecOut {
                    // s % ncs only (workgroup b of the prologue appends to segment (b % (nseg / ncs)) * ncs + covariate): a workgroup of the count kernel
                    // then meets ONE covariate at a time and its private table needs that covariate's rows only
 };
-// k_bqsr_prologue_fast's workgroups take PF_TILES * 256 consecutive staged records, thread t of a workgroup the records t, t + 256, ...;
-// k_c3_seg_hist walks the RGID column in the same workgroups to size the covariate-split segments exactly
-constexpr int PF_TILES = 16;
 __device__ __forceinline__ void rec_pack_idx(BqRec &r, uint32_t idx) {
   r.ref_hi = (r.ref_hi & 0xFFFFu) | (idx << 16);
   r.fl = (r.fl & ~(0x3FFu << 14)) | (((idx >> 16) & 0x3FFu) << 14);
@@ -322,10 +319,52 @@ struct Count3Args {
   unsigned long long *cycle_tbl, *ctx_tbl;
   uint32_t *err;
 };
-int count3_plan(int n_cov, int n_q, int lmax, int *rsw_out, int *rlog_out, size_t *dyn_out, int force_rlog = -1);
 int count3_launch(elp_ctx *c, const Count3Args &A, const QMap &qm, size_t dyn);
+
+// ---- the general count kernel (bqsr_count.hip)
+struct CountArgs {
+  uint64_t n, qual_bytes;
+  const uint64_t *qual_off, *seq_off;
+  const uint8_t *qual, *seq4;
+  const BqDesc *desc;
+  const uint32_t *cigar, *cig_scratch;
+  const uint8_t *skipbits;  // the skip-bit column: bit (QUAL offset of the base)
+  uint8_t *const *ref_seq;  // packed (k_pack_reference)
+  const int64_t *ref_seq_len;
+  int n_ref, n_cov, n_q, lmax, rs, max_cycle;  // rs = row stride of the private table (u32 words)
+  unsigned long long *cycle_tbl, *ctx_tbl;  // dense int64 tables of the C ABI (device copies)
+  uint32_t *err;
+  const uint32_t *tile_first;
+  // this pass counts the reads of covariates [cov0, cov0 + n_cov) only (n_cov above = the covariates of the PASS): with many read groups
+  // the rows of all covariates do not fit one workgroup's LDS, the host then runs one pass per covariate subset - the reference's maps
+  // just grow (filters/bqsr.go:467-551)
+  int cov0;
+};
+
+int count_general_launch(elp_ctx *c, const CountArgs &A, const QMap &qm, const CountPlan &p, size_t dyn);
+int qual_from_cycle_launch(elp_ctx *c, int ncyc_g, const unsigned long long *cycle_tbl, unsigned long long *qual_tbl);
+// count3.hip's records: `block` is the gather's scratch block (GatherScratch)
+int c3_segments_launch(elp_ctx *c, const GatherScratch &S, uint32_t *block, uint32_t nseg, uint32_t ncs);
+int c3_other_sort_launch(elp_ctx *c, const uint4 *other, const uint32_t *n_other, uint32_t *cw, uint4 *sorted);
+
+// ---- the prologue passes (bqsr_prologue.hip)
+struct PrologueBufs {
+  BqDesc *desc;       // a descriptor per staged record
+  uint32_t *skipbits; // the 1-bit-per-base known-site column
+  uint32_t *block;    // the gather's scratch block (GatherScratch): the two lists and their counts
+  uint32_t *cs_pool;  // clipped CIGARs of the general pass
+  uint4 *plain_rec;   // a 64-byte line per staged read, written for the reads with indels only (pf_record<false> -> k_bqsr_prologue_plain)
+};
+int prologue_launch(elp_ctx *c, const PrologueBufs &b, const GatherScratch &S, const RecOut &ro);
+
+// ---- static LDS of the kernels the plans of bqsr_plan.hpp budget for, each defined beside its kernel's __shared__ declarations
+extern const size_t COUNT3_STATIC_LDS;                        // count3.hip: k_bqsr_count3
+extern const size_t COUNT_STATIC_LDS, COUNT_STATIC_LDS_1024;  // bqsr_count.hip: k_bqsr_count with 512 / 1024 threads
+extern const size_t APPLY3_STATIC_LDS;                        // apply3.hip: k_bqsr_apply3
+
+int bqsr_error(elp_ctx *c, uint32_t e);  // bqsr.hip: the device error word as the call's error
+
 // ---- ApplyBQSR for read sets of one length (apply3.hip)
-int apply3_bytes(int n_cov, int n_qi, int lmax, size_t *dyn_out);
 int apply3_launch(elp_ctx *c, int max_cycle, const uint8_t *d_lut, const uint8_t *d_cov_present, const uint16_t *t1, const uint8_t *t2, const uint32_t *n_dict_dev,
                   int n_qi, int lmax, size_t dyn, bool split /* records sorted by covariate, per-covariate row dictionaries */);
 

@@ -201,7 +201,7 @@ struct elp_ctx {
   hipEvent_t lut_ev = nullptr;
   hipEvent_t apply_ev = nullptr;   // behind the last elp_bqsr_apply that read lut_dev / lut_wk: the next upload's copy waits for it
   int lut_uploaded_cycle = 0;
-  // the row dictionary of the uploaded LUT (bqsr.hip: lut_dictionary), built on the copy stream behind the upload when the facts it needs
+  // the row dictionary of the uploaded LUT (bqsr_apply.hip: lut_uploaded), built on the copy stream behind the upload when the facts it needs
   // are known at that time; elp_bqsr_apply uses it if they still hold
   elp::DVec<uint32_t> lut_wk;
   bool dict_ready = false;

@@ -1,7 +1,7 @@
 // count3.hip — the BQSR covariate count for read sets of one length (what a sequencer writes), round 3.
 //
-// Reference: BaseRecalibrator.Recalibrate's per-base loop (filters/bqsr.go:505-538) over the records the prologue kernels of bqsr.hip
-// prepared (recalibrateAln, clipping, known-site bits).  Same tables as k_bqsr_count (bqsr.hip), which stays as the general kernel:
+// Reference: BaseRecalibrator.Recalibrate's per-base loop (filters/bqsr.go:505-538) over the records the prologue kernels of bqsr_prologue.hip
+// prepared (recalibrateAln, clipping, known-site bits).  Same tables as k_bqsr_count (bqsr_count.hip), which stays as the general kernel:
 // ragged read lengths, reads longer than --max-cycle or 1022 bases, more quality slots than one table pass holds.
 //
 // What the measurements of this round said (profiles/r3m_isa_rate_probe.txt, profiles/r3o_count2_ab_and_ablations.txt):
@@ -38,7 +38,7 @@
 namespace elp {
 
 constexpr uint32_t N1 = 0x11111111u, C3 = 0x33333333u;
-constexpr int C3_XROWS = 3, C3_PAD = 64, C3_NT = 1024;
+constexpr int C3_NT = 1024;  // (C3_XROWS, C3_PAD: bqsr_plan.hpp)
 
 template <int BYTE>
 __device__ __forceinline__ uint32_t byte_shl2(uint32_t w, uint32_t two) {  // ((w >> 8 BYTE) & 0xFF) << 2 in one instruction
@@ -332,6 +332,13 @@ struct Count3 {
   }
 };
 
+// The static LDS count3_plan (bqsr_plan.hpp) sets aside for k_bqsr_count3: the kernel's __shared__ arrays, term by term (the kernel asserts
+// the sum against its own declarations), and a margin for the padding between them.
+constexpr size_t COUNT3_LDS_ARRAYS = 2 * sizeof(uint32_t[256]) + sizeof(uint8_t[96]) + sizeof(uint32_t[C3_MAXSEG]) + sizeof(uint32_t[C3_MAXSEG + 1]) + sizeof(uint32_t[4]);
+constexpr size_t COUNT3_LDS = COUNT3_LDS_ARRAYS + 256 + 12;
+extern const size_t COUNT3_STATIC_LDS = COUNT3_LDS;
+static_assert(COUNT3_LDS == 1024 + 1024 + 96 + 256 + (2 * C3_MAXSEG + 8) * 4, "the budget the plan was written around");
+
 template <int RLOG, bool OTHER>
 __global__ __launch_bounds__(C3_NT) void k_bqsr_count3(Count3Args A, QMap qm) {
   __shared__ uint32_t qrow[256];
@@ -380,6 +387,8 @@ __global__ __launch_bounds__(C3_NT) void k_bqsr_count3(Count3Args A, QMap qm) {
   B.nb = len - B.k0 < 16u ? len - B.k0 : 16u;
   // trips per segment, their exclusive prefix sums (s_pre[k] for k >= nseg = the total)
   __shared__ uint32_t s_cnt[C3_MAXSEG], s_pre[C3_MAXSEG + 1], s_wsum[4];
+  static_assert(sizeof(qrow) + sizeof(spread8) + sizeof(slot_q) + sizeof(s_cnt) + sizeof(s_pre) + sizeof(s_wsum) == COUNT3_LDS_ARRAYS,
+                "COUNT3_LDS_ARRAYS lists the kernel's __shared__ arrays: add a new one there too");
   {
     const uint32_t my_cnt = threadIdx.x < A.nseg ? A.seg_cnt[(size_t)threadIdx.x * A.cnt_stride] : 0u;
     const uint32_t my_trips = (my_cnt + RPI - 1u) / RPI;
@@ -491,24 +500,6 @@ __global__ __launch_bounds__(C3_NT) void k_bqsr_count3(Count3Args A, QMap qm) {
     for (int d = 32; d >= 1; d >>= 1) my_err |= __shfl_xor(my_err, d, 64);
     if ((threadIdx.x & 63) == 0) atomicOr(&A.err[0], my_err);
   }
-}
-
-// Launch plan: one workgroup of 1024 threads per CU around one table; the context cells are replicated as often as the CU's LDS allows.
-// Returns 1 if the tables of this pass do not fit (the caller uses k_bqsr_count).
-int count3_plan(int n_cov, int n_q, int lmax, int *rsw_out, int *rlog_out, size_t *dyn_out, int force_rlog) {
-  const size_t lds_cu = 160 * 1024, static_lds = 1024 + 1024 + 96 + 256 + (2 * C3_MAXSEG + 8) * 4;
-  const int ncw = ((17 * 2 * lmax) >> 4) + 2;
-  const size_t rows = (size_t)n_cov * (size_t)(n_q + C3_XROWS);
-  for (int rlog = 5; rlog >= 1; rlog--) {
-    if (force_rlog >= 0 && force_rlog != rlog) continue;  // elp_set_tuning "count3_rlog": measurements only
-    const int rsw = ((16 << rlog) + 16 + ncw + 31) & ~31;
-    const size_t dyn = (rows * (size_t)rsw + C3_PAD) * 4;
-    if (dyn + static_lds <= lds_cu && rows * (size_t)rsw * 4 < (1u << 22)) {
-      *rsw_out = rsw; *rlog_out = rlog; *dyn_out = dyn;
-      return 0;
-    }
-  }
-  return 1;
 }
 
 int count3_launch(elp_ctx *c, const Count3Args &A, const QMap &qm, size_t dyn) {

@@ -1,6 +1,6 @@
 """GPU parity tests (-m gpu) on every CIGAR operation: =, X, P, N (introns up to 200 kb), zero-length M / I / D / P, leading and trailing
 I or D, I next to D - next to the M / I / D / S / H of the other generators.  The device branches on these letters in the BQSR prologue
-routing (fast: [H][S](M|=|X)[S][H]; plain: two to five ops of M / = / X / I / D; general: the rest, bqsr.hip), the reference pieces,
+routing (fast: [H][S](M|=|X)[S][H]; plain: two to five ops of M / = / X / I / D; general: the rest, bqsr_prologue.hip), the reference pieces,
 the read coordinate of a known site next to a D, the unclipped 5' position of a reverse read (an N counts), the filter predicates,
 CleanSam and the BAM emitter's bin.  Every output is compared bit for bit with the CPU oracle."""
 import functools
@@ -72,7 +72,7 @@ def _fit(ops, L):
 
 
 def route(ops):
-    """the prologue a read of this (staged) CIGAR takes, by the rule of k_bqsr_prologue (bqsr.hip): 'fast', 'plain' or 'general'"""
+    """the prologue a read of this (staged) CIGAR takes, by the rule of k_bqsr_prologue_fast (bqsr_prologue.hip): 'fast', 'plain' or 'general'"""
     nop = len(ops)
     simple, k, mlen = 1 <= nop <= 5, 0, 0
     if simple and ops[0][1] == "H":

@@ -1,7 +1,7 @@
 """GPU tests (-m gpu) that drive the private LDS tables of the two BQSR count kernels to the capacity of their packed counters and through
 their in-loop flushes.  A cycle cell is 16 | 16 bits (observations | mismatches; in the general kernel's MG form two 16-bit observation
 cells of neighbouring cycles share a word), and only the flush schedule keeps one half from carrying into the other:
-  k_bqsr_count   (bqsr.hip)   flushes at the end of the first 32768-byte index tile behind which more than 30000 reads have started since
+  k_bqsr_count   (bqsr_count.hip)   flushes at the end of the first 32768-byte index tile behind which more than 30000 reads have started since
                               the last flush: at most 30000 + 32768 = 62768 counts per cell;
   k_bqsr_count3  (count3.hip) flushes every 30000 / (RPI + 1) + 1 trips of RPI = 1024 / ceil(len / 16) reads: at most flush_every x RPI
                               (30720 for reads of up to 16 bases) per cell, and at every segment's end under the covariate split.
@@ -150,7 +150,7 @@ def _same(got, want):
 # r = 29999 / 30000: no flush behind tile 0, cell (30, cycle 1) holds 62767 / 62768 - the design's maximum - at the end of tile 1;
 # r = 30001 / 32768: a flush behind tile 0 and one behind tile 1; 32768 = two full tiles is the one that a threshold above a tile's
 # reads (or a flush at the end of the step only) overflows: 65536 counts.
-# Private-table forms (the plan in gather_impl, bqsr.hip), by (read groups, qualities of the long reads); rows of 352 words at 150 bases:
+# Private-table forms (count_general_plan, bqsr_plan.hpp), by (read groups, qualities of the long reads); rows of 352 words at 150 bases:
 FORMS = {
     "wg512": (1, 5),    # 9 rows of 1408 B: three 512-thread workgroups per CU
     "big": (2, 20),     # 2 x 24 rows = 68 KB: more than half a CU's LDS -> one 1024-thread workgroup, 16 | 16 cells, one pass
