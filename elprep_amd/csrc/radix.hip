@@ -176,62 +176,92 @@ constexpr unsigned long long RS_AGG = 1ull << 32, RS_INCL = 2ull << 32;
 
 // PAIRS = false: no values - the sort's elements are single words, e.g. key << b | index (`fuse` = b > 0: this pass reads bare keys and
 // appends the element's index: the first pass of such a sort); 16 instead of 24 bytes per element and pass.
-template <int THREADS, bool PAIRS>
-__global__ __launch_bounds__(THREADS, THREADS >= 512 ? 4 : 1) void k_radix_scatter_t(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals,
-                                                              uint64_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out, uint64_t n,
-                                                              int shift, const unsigned long long *__restrict__ ghist /* [256] of this digit */,
-                                                              unsigned long long *state, uint32_t epoch, uint32_t *ticket,
-                                                              uint32_t *err, const uint32_t *__restrict__ n_dev, int fuse, RadixBounds bnd) {
-  constexpr int WAVES = THREADS / 64, TILE = THREADS * RS_ITEMS;  // 4096 keys (256 threads) or 8192 (512: runs of twice the length per digit)
-  __shared__ uint32_t cnt[WAVES][256];
-  __shared__ uint32_t gbase[256];   // global position of the tile's first key with digit d, minus its position inside the sorted tile
-  __shared__ uint32_t scan_lds[16];
-  // the tile in digit order: keys first, then (as uint32) the values - 32 KB static, or 64 KB of dynamic LDS
-  extern __shared__ __attribute__((aligned(16))) uint64_t sbuf_dyn[];
-  __shared__ uint64_t sbuf_static[THREADS == 256 ? RS_TILE : 1];
-  uint64_t *const sbuf = THREADS == 256 ? sbuf_static : sbuf_dyn;
-  __shared__ uint32_t my_tile;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (threadIdx.x == 0) my_tile = atomicAdd(ticket, 1u);  // tiles are numbered in the order they start (the host zeroes the counter)
-  for (int i = threadIdx.x; i < WAVES * 256; i += THREADS) (&cnt[0][0])[i] = 0;
-  __syncthreads();
-  const uint32_t tile = my_tile;
+//
+// The body of one tile.  FULL = the tile holds TILE keys (every tile but the array's last one): no lane is ever invalid, so the loads are
+// unconditional and the validity compares, selects and masks of the general form are not compiled in.  The kernel is bound by vector
+// issue, not by bandwidth, so what is counted here is vector instructions per key:
+//  - `tile` and the wave number are wave-uniform values in scalar registers: a wave's keys are read through a scalar base pointer plus a
+//    32-bit lane offset, the rounds differ in the instruction's immediate offset only;
+//  - ranking: per digit bit one sign-extended bit s (0 / ~0) and one ballot m; lanes whose bit differs from lane j's are m ^ s, OR-ed over the
+//    eight bits (three-operand OR), the complement are the peers.  The rank among the peers is mbcnt; EVERY lane reads the wave's counter
+//    of its digit (peers read one address: a broadcast) and the first peer - the one with no peer below it - writes it back increased,
+//    so no find-first and no cross-lane fetch is needed.  (LDS instructions of one wave execute in program order.)
+template <int THREADS, bool PAIRS, bool FULL>
+__device__ __forceinline__ void radix_scatter_tile(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals, uint64_t *__restrict__ keys_out,
+                                                   uint32_t *__restrict__ vals_out, const uint32_t tile, const uint32_t tile_n, const int shift,
+                                                   const unsigned long long *__restrict__ ghist, unsigned long long *state, const uint32_t epoch,
+                                                   uint32_t *err, const int fuse, const RadixBounds bnd, uint32_t (*cnt)[256], uint32_t *gbase,
+                                                   uint32_t *scan_lds, uint64_t *sbuf) {
+  constexpr int WAVES = THREADS / 64, TILE = THREADS * RS_ITEMS, WTILE = 64 * RS_ITEMS;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint64_t tbase = (uint64_t)tile * TILE;
-  if (n_dev) {  // device-side length: the launch covers its upper bound, tiles behind the end leave at once (nobody looks back at them)
-    n = *n_dev;
-    if (tbase >= n) return;
-  }
-  const uint64_t wbase = tbase + (uint64_t)w * (64 * RS_ITEMS);
-  const uint32_t tile_n = (uint32_t)((n - tbase) < (uint64_t)TILE ? (n - tbase) : (uint64_t)TILE);
+  const uint32_t wofs = w * WTILE;                   // the wave's first key inside the tile
+  const int wn = FULL ? WTILE : (int)tile_n - (int)wofs;  // the wave's keys (<= 0: none); lane `l` of round r is valid if r * 64 + l < wn
+  const uint64_t *const wkeys = keys + tbase + wofs;
+  const uint32_t *const wvals = vals ? vals + tbase + wofs : nullptr;
+  const uint32_t widx = (uint32_t)tbase + wofs;      // index of the wave's first key (the callers keep n below 2^32)
+  uint32_t *const wcnt = cnt[w];
   uint64_t k[RS_ITEMS];
   uint32_t v[PAIRS ? RS_ITEMS : 1];
   uint32_t pos[RS_ITEMS];
-  const unsigned long long lt_mask = (1ull << lane) - 1ull;
 #pragma unroll
   for (int r = 0; r < RS_ITEMS; r++) {
-    uint64_t i = wbase + (uint64_t)r * 64 + lane;
-    bool valid = i < n;
-    k[r] = valid ? keys[i] : ~0ull;
-    if (!PAIRS && fuse && valid) k[r] = (k[r] << fuse) | i;
-    if (PAIRS) v[r] = valid ? (vals ? vals[i] : (uint32_t)i) : 0u;  // no value array: the values are the indices (first pass of a sort)
-    uint32_t d = (uint32_t)(k[r] >> shift) & 0xFF;
-    // peers = lanes of this wave holding the same digit this round (invalid lanes form their own class)
-    unsigned long long peers = __ballot(valid);
-    peers = valid ? peers : ~peers;
+    const uint32_t o = (uint32_t)r * 64u + lane;
+    const bool valid = FULL || (int)o < wn;
+    k[r] = valid ? wkeys[o] : ~0ull;
+    if (PAIRS) v[r] = valid ? (wvals ? wvals[o] : widx + o) : 0u;  // no value array: the values are the indices (first pass of a sort)
+  }
+  if (!PAIRS && fuse) {
 #pragma unroll
-    for (int b = 0; b < 8; b++) {
-      unsigned long long m = __ballot((d >> b) & 1);
-      peers &= ((d >> b) & 1) ? m : ~m;
+    for (int r = 0; r < RS_ITEMS; r++) {
+      const uint32_t o = (uint32_t)r * 64u + lane;
+      if (FULL || (int)o < wn) k[r] = (k[r] << fuse) | (uint64_t)(widx + o);
     }
-    uint32_t before = (uint32_t)__popcll(peers & lt_mask);
-    int leader = __ffsll((long long)peers) - 1;
-    uint32_t old = 0;
-    if (valid && lane == leader) {
-      old = cnt[w][d];
-      cnt[w][d] = old + (uint32_t)__popcll(peers);
+  }
+#pragma unroll
+  for (int r0 = 0; r0 < RS_ITEMS; r0 += 2) {
+    // two rounds at a time: their ballots do not depend on each other, so one round's instructions fill the wait states between the
+    // other's compare and the use of its mask; only the counters' read-modify-writes below are in order
+    uint32_t ds[2], peers_lo[2], peers_hi[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      ds[h] = (uint32_t)(k[r0 + h] >> shift);  // the digit in bits 7:0
+      // peers = lanes of this wave holding the same digit this round, among the valid ones (an invalid lane's rank is never used)
+      uint32_t diff_lo = 0, diff_hi = 0;
+#pragma unroll
+      for (int b = 0; b < 8; b++) {
+        int s = __builtin_amdgcn_sbfe(ds[h], b, 1);
+        asm("" : "+v"(s));  // (keeps the ballot's compare on s: one instruction, not a shift and a sign test of ds next to the bfe)
+        const unsigned long long m = __ballot(s != 0);
+        // diff | (m ^ s) in one three-input bit operation (table 0xF6); the last bit's form is its complement (0x09): the peers
+        if (b < 7) {
+          diff_lo = __builtin_amdgcn_bitop3_b32(diff_lo, (uint32_t)m, (uint32_t)s, 0xF6);
+          diff_hi = __builtin_amdgcn_bitop3_b32(diff_hi, (uint32_t)(m >> 32), (uint32_t)s, 0xF6);
+        } else {
+          peers_lo[h] = __builtin_amdgcn_bitop3_b32(diff_lo, (uint32_t)m, (uint32_t)s, 0x09);
+          peers_hi[h] = __builtin_amdgcn_bitop3_b32(diff_hi, (uint32_t)(m >> 32), (uint32_t)s, 0x09);
+        }
+      }
     }
-    old = __shfl(old, leader, 64);
-    pos[r] = old + before;  // rank among the wave's keys with this digit
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const int r = r0 + h;
+      const bool valid = FULL || (int)((uint32_t)r * 64u + lane) < wn;
+      if (!FULL) {
+        const unsigned long long vm = __ballot(valid);
+        peers_lo[h] &= (uint32_t)vm;
+        peers_hi[h] &= (uint32_t)(vm >> 32);
+      }
+      const uint32_t before = __builtin_amdgcn_mbcnt_hi(peers_hi[h], __builtin_amdgcn_mbcnt_lo(peers_lo[h], 0u));
+      const uint32_t d = ds[h] & 0xFF;
+      uint32_t old = 0;
+      if (valid) {
+        old = wcnt[d];
+        if (before == 0) wcnt[d] = old + (uint32_t)__popc(peers_lo[h]) + (uint32_t)__popc(peers_hi[h]);
+      }
+      pos[r] = old + before;  // rank among the wave's keys with this digit
+    }
   }
   __syncthreads();
   // thread t owns digit t: position of the digit inside the sorted tile (exclusive scan over digits), then per-wave starts
@@ -264,10 +294,9 @@ __global__ __launch_bounds__(THREADS, THREADS >= 512 ? 4 : 1) void k_radix_scatt
   // keys into digit order
 #pragma unroll
   for (int r = 0; r < RS_ITEMS; r++) {
-    uint64_t i = wbase + (uint64_t)r * 64 + lane;
-    if (i < n) {
+    if (FULL || (int)((uint32_t)r * 64u + lane) < wn) {
       uint32_t d = (uint32_t)(k[r] >> shift) & 0xFF;
-      pos[r] += cnt[w][d];
+      pos[r] += wcnt[d];
       sbuf[pos[r]] = k[r];
     }
   }
@@ -309,7 +338,7 @@ __global__ __launch_bounds__(THREADS, THREADS >= 512 ? 4 : 1) void k_radix_scatt
 #pragma unroll
   for (int r = 0; r < RS_ITEMS; r++) {
     const uint32_t j = (uint32_t)r * THREADS + threadIdx.x;
-    if (j < tile_n) {
+    if (FULL || j < tile_n) {
       const uint64_t key = sbuf[j];
       dst[r] = gbase[(uint32_t)(key >> shift) & 0xFF] + j;
       keys_out[dst[r]] = key;
@@ -332,15 +361,45 @@ __global__ __launch_bounds__(THREADS, THREADS >= 512 ? 4 : 1) void k_radix_scatt
   uint32_t *sval = reinterpret_cast<uint32_t *>(sbuf);
 #pragma unroll
   for (int r = 0; r < RS_ITEMS; r++) {
-    uint64_t i = wbase + (uint64_t)r * 64 + lane;
-    if (i < n) sval[pos[r]] = v[PAIRS ? r : 0];
+    if (FULL || (int)((uint32_t)r * 64u + lane) < wn) sval[pos[r]] = v[PAIRS ? r : 0];
   }
   __syncthreads();
 #pragma unroll
   for (int r = 0; r < RS_ITEMS; r++) {
     const uint32_t j = (uint32_t)r * THREADS + threadIdx.x;
-    if (j < tile_n) vals_out[dst[r]] = sval[j];
+    if (FULL || j < tile_n) vals_out[dst[r]] = sval[j];
   }
+}
+
+template <int THREADS, bool PAIRS>
+__global__ __launch_bounds__(THREADS, THREADS >= 512 ? 4 : 1) void k_radix_scatter_t(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals,
+                                                              uint64_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out, uint64_t n,
+                                                              int shift, const unsigned long long *__restrict__ ghist /* [256] of this digit */,
+                                                              unsigned long long *state, uint32_t epoch, uint32_t *ticket,
+                                                              uint32_t *err, const uint32_t *__restrict__ n_dev, int fuse, RadixBounds bnd) {
+  constexpr int WAVES = THREADS / 64, TILE = THREADS * RS_ITEMS;  // 4096 keys (256 threads) or 8192 (512: runs of twice the length per digit)
+  __shared__ uint32_t cnt[WAVES][256];
+  __shared__ uint32_t gbase[256];   // global position of the tile's first key with digit d, minus its position inside the sorted tile
+  __shared__ uint32_t scan_lds[16];
+  // the tile in digit order: keys first, then (as uint32) the values - 32 KB static, or 64 KB of dynamic LDS
+  extern __shared__ __attribute__((aligned(16))) uint64_t sbuf_dyn[];
+  __shared__ uint64_t sbuf_static[THREADS == 256 ? RS_TILE : 1];
+  uint64_t *const sbuf = THREADS == 256 ? sbuf_static : sbuf_dyn;
+  __shared__ uint32_t my_tile;
+  if (threadIdx.x == 0) my_tile = atomicAdd(ticket, 1u);  // tiles are numbered in the order they start (the host zeroes the counter)
+  for (int i = threadIdx.x; i < WAVES * 256; i += THREADS) (&cnt[0][0])[i] = 0;
+  __syncthreads();
+  const uint32_t tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)my_tile);  // (one value per workgroup: into a scalar register)
+  const uint64_t tbase = (uint64_t)tile * TILE;
+  if (n_dev) {  // device-side length: the launch covers its upper bound, tiles behind the end leave at once (nobody looks back at them)
+    n = *n_dev;
+    if (tbase >= n) return;
+  }
+  const uint32_t tile_n = (uint32_t)((n - tbase) < (uint64_t)TILE ? (n - tbase) : (uint64_t)TILE);
+  if (tile_n == (uint32_t)TILE)
+    radix_scatter_tile<THREADS, PAIRS, true>(keys, vals, keys_out, vals_out, tile, tile_n, shift, ghist, state, epoch, err, fuse, bnd, cnt, gbase, scan_lds, sbuf);
+  else
+    radix_scatter_tile<THREADS, PAIRS, false>(keys, vals, keys_out, vals_out, tile, tile_n, shift, ghist, state, epoch, err, fuse, bnd, cnt, gbase, scan_lds, sbuf);
 }
 
 // state words, ticket counters and the epoch of one more pass over `ntiles` tiles
@@ -361,9 +420,9 @@ static int radix_next_epoch(elp_ctx *c) {
 }
 
 // one pass.  Tiles of 16384 keys (1024 threads, 128 KB of LDS: one workgroup per CU) for arrays of 16 M elements and more, of 8192 from 4 M
-// on - a digit's keys leave a tile as runs of four times / twice the length: 50 M pairs, four passes: 2.14 ms (4096), 2.01 (8192), 1.81
-// (16384) -, of 4096 for the short ones (more tiles than CUs matter more there); elp_set_tuning "radix_tile": 1 / 2 / 3 = 4096 / 8192 /
-// 16384 always
+// on - a digit's keys leave a tile as runs of four times / twice the length: the coordinate sort's four passes over 50.2 M words take 0.98 ms
+// with 16384 and 1.01 with 8192 (1.48 / 1.57 before the ranking was cut: profiles/radix_scatter_ab.txt) -, of 4096 for the short ones
+// (more tiles than CUs matter more there); elp_set_tuning "radix_tile": 1 / 2 / 3 = 4096 / 8192 / 16384 always
 static int radix_tile_shift(const elp_ctx *c, uint64_t n) {  // tile = 4096 keys << shift
   if (c->tune.radix_tile >= 1 && c->tune.radix_tile <= 3) return c->tune.radix_tile - 1;
   return n >= (16ull << 20) ? 2 : n >= (4ull << 20) ? 1 : 0;
