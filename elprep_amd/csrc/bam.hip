@@ -200,7 +200,6 @@ __device__ inline uint32_t out_size(const BamOut &m, uint32_t i, uint32_t *err) 
 }
 // Output record k of a MERGED stream (elp_emit_merged_bam) comes from one of two contexts: src[k] = rank of the record in the first
 // context's sorted output, or MERGE_SECOND | its rank in the second's.  src == nullptr: one context, output record k = perm[k].
-constexpr uint32_t MERGE_SECOND = 0x80000000u;
 __device__ __forceinline__ const BamOut &out_source(const BamOut &m, const BamOut &m2, const uint32_t *__restrict__ src, uint64_t k, uint32_t *i) {
   if (!src) { *i = m.perm[k]; return m; }
   const uint32_t s = src[k];
@@ -651,7 +650,7 @@ static uint64_t out_growth(const elp_ctx *c) { return c->replace_rg ? 4 + (uint6
 int elp_emit_sorted_bam(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
   if (!c || !n_bytes_out) return ELP_ERR_ARG;
   ELP_HIP(c, hipSetDevice(c->device));
-  if (!c->derived.sorted) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bam: call elp_sort_coordinate or elp_sort_queryname first");
+  if (!c->derived.sorted) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bam: call elp_sort_coordinate, elp_sort_queryname or elp_order_keep first");
   ELP_TRY(radix_check(c));
   if (c->raw_n != c->n) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bam: records were not staged with elp_stage_bam");
   const BamOut m = bam_out_of(c);
@@ -666,7 +665,7 @@ int elp_emit_sorted_bam(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_byte
 int elp_emit_sorted_bgzf(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
   if (!c || !n_bytes_out) return ELP_ERR_ARG;
   ELP_HIP(c, hipSetDevice(c->device));
-  if (!c->derived.sorted) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bgzf: call elp_sort_coordinate or elp_sort_queryname first");
+  if (!c->derived.sorted) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bgzf: call elp_sort_coordinate, elp_sort_queryname or elp_order_keep first");
   ELP_TRY(radix_check(c));
   if (c->raw_n != c->n) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bgzf: records were not staged with elp_stage_bam");
   const BamOut m = bam_out_of(c);
@@ -687,20 +686,32 @@ __global__ __launch_bounds__(256) void k_merge_fill(uint64_t n_out, const uint32
   if (s < n_out && !is_spread[s]) src[s] = (uint32_t)s - before[s];  // group reads fill the remaining slots in order
 }
 
-int elp_emit_merged_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
-  if (!groups || !spread || groups == spread || !n_bytes_out) return ELP_ERR_ARG;
-  if (groups->derived.sorted_qname || spread->derived.sorted_qname) return merge_refuses_queryname(groups, "elp_emit_merged_bam");
-  if (groups->raw_n != groups->n || spread->raw_n != spread->n) return set_error(groups, ELP_ERR_ARG, "elp_emit_merged_bam: records were not staged with elp_stage_bam");
+// what a stream made of two contexts asks of them (elp_emit_merged_*, elp_emit_concat_*)
+static int two_context_checks(elp_ctx *groups, elp_ctx *spread, const char *who) {
+  if (groups->raw_n != groups->n || spread->raw_n != spread->n) return set_error(groups, ELP_ERR_ARG, "%s: records were not staged with elp_stage_bam", who);
   // one stream, one filter: the tag filter (and the replacing read group) of `groups`, which `spread` must share
   if (groups->tag_filter != spread->tag_filter || (groups->tag_filter && groups->h_tag_drop != spread->h_tag_drop))
-    return set_error(groups, ELP_ERR_ARG, "elp_emit_merged_bam: the two contexts' tag filters differ (elp_set_tag_filter)");
-  if (!same_replace_rg(groups, spread)) return set_error(groups, ELP_ERR_ARG, "elp_emit_merged_bam: the two contexts' replacing read groups differ (elp_set_replace_read_group)");
+    return set_error(groups, ELP_ERR_ARG, "%s: the two contexts' tag filters differ (elp_set_tag_filter)", who);
+  if (!same_replace_rg(groups, spread)) return set_error(groups, ELP_ERR_ARG, "%s: the two contexts' replacing read groups differ (elp_set_replace_read_group)", who);
   if (groups->dict_replaced != spread->dict_replaced)
-    return set_error(groups, ELP_ERR_ARG, "elp_emit_merged_bam: one context has replaced its reference dictionary, the other has not (elp_replace_reference_dictionary)");
+    return set_error(groups, ELP_ERR_ARG, "%s: one context has replaced its reference dictionary, the other has not (elp_replace_reference_dictionary)", who);
+  return 0;
+}
+static int emit_two(elp_ctx *groups, elp_ctx *spread, const uint32_t *src, uint64_t n_out, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out, bool bgzf) {
+  const BamOut mg = bam_out_of(groups);
+  BamOut ms = bam_out_of(spread);
+  ms.drop = mg.drop; ms.rg_new = mg.rg_new;  // (equal contents, checked by two_context_checks; both on this device)
+  return emit_stream(groups, mg, ms, src, n_out, std::max(groups->max_raw_rec, spread->max_raw_rec) + out_growth(groups), out, cap, n_bytes_out, bgzf);
+}
+
+static int emit_merged(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out, bool bgzf, const char *who) {
+  if (!groups || !spread || groups == spread || !n_bytes_out) return ELP_ERR_ARG;
+  if (groups->derived.sorted_qname || spread->derived.sorted_qname) return merge_refuses_queryname(groups, who);
+  ELP_TRY(two_context_checks(groups, spread, who));
   uint64_t *slots = nullptr;
-  ELP_TRY(merge_spread_slots(groups, spread, &slots));  // checks: both sorted, one device
+  ELP_TRY(merge_spread_slots(groups, spread, &slots));  // checks: both coordinate-sorted or keep-ordered (then: monotonic), one device
   const uint64_t ng = groups->n - groups->n_sr, ns = spread->n - spread->n_sr, n_out = ng + ns;
-  if (n_out >= MERGE_SECOND) return set_error(groups, ELP_ERR_UNSUPPORTED, "elp_emit_merged_bam: more than 2^31 output records");
+  if (n_out >= MERGE_SECOND) return set_error(groups, ELP_ERR_UNSUPPORTED, "%s: more than 2^31 output records", who);
   if (n_out == 0) { *n_bytes_out = 0; return 0; }
   uint32_t *w;
   ELP_TRY(scratch(groups, 6, 3 * (n_out + 8), &w));
@@ -710,10 +721,42 @@ int elp_emit_merged_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t
   if (ns) ELP_LAUNCH(groups, "merge_mark", k_merge_mark, dim3(blocks_for(ns, 256)), dim3(256), 0, ns, (const uint64_t *)slots, is_spread, src);
   ELP_TRY(exclusive_scan_u32(groups, is_spread, before, n_out, nullptr));
   ELP_LAUNCH(groups, "merge_fill", k_merge_fill, dim3(blocks_for(n_out, 256)), dim3(256), 0, n_out, (const uint32_t *)is_spread, (const uint32_t *)before, src);
-  const BamOut mg = bam_out_of(groups);
-  BamOut ms = bam_out_of(spread);
-  ms.drop = mg.drop; ms.rg_new = mg.rg_new;  // (equal contents, checked above; both on this device)
-  return emit_stream(groups, mg, ms, src, n_out, std::max(groups->max_raw_rec, spread->max_raw_rec) + out_growth(groups), out, cap, n_bytes_out);
+  return emit_two(groups, spread, src, n_out, out, cap, n_bytes_out, bgzf);
+}
+
+// MergeUnsortedFilesSplitPerChromosome (sam/split-merge.go:581-619) with payloads: the unmapped file (split id 0 of `groups`), the spread
+// file, then the group files in index order, each in its own (input) order
+static int emit_concat(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out, bool bgzf, const char *who) {
+  if (!groups || !spread || groups == spread || !n_bytes_out) return ELP_ERR_ARG;
+  if (!groups->derived.sorted_keep || !groups->derived.sorted_keep_by_split)
+    return set_error(groups, ELP_ERR_ARG, "%s: the groups context must hold a keep permutation ordered by split id (elp_order_keep with by_split = 1)", who);
+  if (!spread->derived.sorted_keep || spread->derived.sorted_keep_by_split)
+    return set_error(groups, ELP_ERR_ARG, "%s: the spread context must hold a plain keep permutation (elp_order_keep with by_split = 0)", who);
+  ELP_TRY(two_context_checks(groups, spread, who));
+  if (groups->device != spread->device) return set_error(groups, ELP_ERR_ARG, "%s: contexts on different devices", who);
+  ELP_HIP(groups, hipSetDevice(groups->device));
+  const uint64_t ng = groups->n - groups->n_sr, ns = spread->n - spread->n_sr, n_out = ng + ns;
+  if (n_out >= MERGE_SECOND) return set_error(groups, ELP_ERR_UNSUPPORTED, "%s: more than 2^31 output records", who);
+  if (n_out == 0) { *n_bytes_out = 0; return 0; }
+  uint32_t *w;
+  ELP_TRY(scratch(groups, 6, n_out + 16, &w));
+  ELP_HIP(groups, elp::stream_wait(spread->stream));  // (the spread's permutation is complete)
+  ELP_TRY(keep_concat_src(groups, ng, ns, w + n_out + 8, w));
+  return emit_two(groups, spread, w, n_out, out, cap, n_bytes_out, bgzf);
+}
+
+int elp_emit_merged_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
+  return emit_merged(groups, spread, out, cap, n_bytes_out, false, "elp_emit_merged_bam");
+}
+// The merged stream as BGZF members, as elp_emit_sorted_bgzf frames the sorted one: `sfm`'s final output leaves the device compressed
+int elp_emit_merged_bgzf(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
+  return emit_merged(groups, spread, out, cap, n_bytes_out, true, "elp_emit_merged_bgzf");
+}
+int elp_emit_concat_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
+  return emit_concat(groups, spread, out, cap, n_bytes_out, false, "elp_emit_concat_bam");
+}
+int elp_emit_concat_bgzf(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
+  return emit_concat(groups, spread, out, cap, n_bytes_out, true, "elp_emit_concat_bgzf");
 }
 
 }  // extern "C"

@@ -504,6 +504,10 @@ void group_release(elp_ctx *c);
 int group_sendrecv(elp_ctx *c, int send_peer, const void *send_dev, size_t send_bytes, int recv_peer, void *recv_dev, size_t recv_bytes);  // group.hip
 int tables_written(elp_ctx *c);  // bqsr.hip: dev_tables were just written on c->stream
 int stage_reserve(elp_ctx *c, uint64_t n, uint64_t qb, uint64_t co, uint64_t sb, uint64_t lb);
+// Output record k of a stream made from TWO contexts (bam.hip: elp_emit_merged_*, elp_emit_concat_*): src[k] = rank of the record in the first
+// context's output, or MERGE_SECOND | its rank in the second's
+constexpr uint32_t MERGE_SECOND = 0x80000000u;
+int keep_concat_src(elp_ctx *groups, uint64_t ng, uint64_t ns, uint32_t *g0_dev, uint32_t *src);  // keep.hip: the unsorted merge's stream as such an array
 int merge_refuses_queryname(elp_ctx *groups, const char *who);  // filter.hip: ELP_ERR_UNSUPPORTED (cmd/merge.go:175-176)
 int merge_spread_slots(elp_ctx *groups, elp_ctx *spread, uint64_t **slots_out);  // filter.hip: the merge order as ranks, on the device  // grows the staged columns (ctx.hip)
 int stage_recode_seq(elp_ctx *c, uint64_t from, uint64_t bytes);

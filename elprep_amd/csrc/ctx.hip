@@ -564,7 +564,7 @@ static int d2h(elp_ctx *c, void *dst, const void *src, size_t bytes) {
 
 int elp_get_permutation(elp_ctx *c, uint32_t *out) {
   if (!c || (!out && c->n)) return ELP_ERR_ARG;
-  if (!c->derived.sorted) return set_error(c, ELP_ERR_ARG, "elp_get_permutation: call elp_sort_coordinate or elp_sort_queryname first");
+  if (!c->derived.sorted) return set_error(c, ELP_ERR_ARG, "elp_get_permutation: call elp_sort_coordinate, elp_sort_queryname or elp_order_keep first");
   ELP_TRY(radix_check(c));
   return d2h(c, out, c->perm.p, c->n * sizeof(uint32_t));
 }

@@ -17,7 +17,9 @@ namespace elp {
 //     sample (adapt_sampled) and ApplyBQSR's
 //     records (apply_recs_valid)
 //   permutation: perm (sorted; sorted_qname = it is  coordinate: keys, then QNAME, FLAG, MAPQ, RNEXT, PNEXT, TLEN
-//     in queryname order)                            queryname: QNAME, has_sr
+//     in queryname order; sorted_keep = it is in     queryname: QNAME, has_sr
+//     input order, sorted_keep_by_split = ... split  keep (elp_order_keep): has_sr; with by_split also the split ids
+//     file after split file)
 //   presort: the sort's key passes made ahead        the key column (keys)
 //   marks: FLAG's duplicate bit, mate, pair_win      keys (upos), scores, REFID, FLAG, rgid -> library, split ids, QNAME
 //   quality hint: qual_present                       QUAL (a sample, or the score kernel's), tuning "qual_hint", "qual_hint_drop"
@@ -42,6 +44,8 @@ namespace elp {
 //     current columns.  dictionary_replaced() (elp_replace_reference_dictionary) rewrites REFID / RNEXT, the record states and n_ref: what
 //     fixed_fields_changed() and header_changed() spoil goes (the keys with the key passes made ahead of them, scores, permutation,
 //     marks, ApplyBQSR's records), and the snapshot too - a rollback restores FLAG and QUAL, not the refids they were decided under.
+//   * duplicate_bit_cleared() and flag_qual_restored() drop a keep permutation too although it reads neither FLAG nor QUAL: one rule for
+//     every kind of permutation (conservative; elp_order_keep is cheap to repeat).
 //   * Tuning "score_kernel" clears the scores only (with one `adapted` flag it took the keys along, which do not depend on it).
 struct Derived {
   bool keys = false;
@@ -53,6 +57,8 @@ struct Derived {
   bool presorted = false;          // the coordinate sort's key passes were made ahead from the key column as it is (sort_presort)
   bool sorted = false;
   bool sorted_qname = false;       // the permutation is in queryname order (elp_sort_queryname), not coordinate order
+  bool sorted_keep = false;        // the permutation is in input order (elp_order_keep): no sort made it ...
+  bool sorted_keep_by_split = false;  // ... with the records of one split id behind those of the smaller ids (by_split != 0)
   bool marked = false;
   bool have_qual_present = false;
   bool have_snapshot = false;
@@ -64,12 +70,13 @@ struct Derived {
   bool has_uniform(uint64_t n, uint64_t qual_bytes) const { return uniform_n == n && uniform_bytes == qual_bytes && n; }
 
   // ---- items becoming valid where a flag alone would allow an inconsistent pair
-  void set_sorted(bool by_qname) { sorted = true; sorted_qname = by_qname; }
+  void set_sorted(bool by_qname) { sorted = true; sorted_qname = by_qname; sorted_keep = sorted_keep_by_split = false; }
+  void set_sorted_keep(bool by_split) { sorted = sorted_keep = true; sorted_keep_by_split = by_split; sorted_qname = false; }
   void adapt_word_read(bool bad_qual) { adapt_pending = false; if (bad_qual) adapt_bad_qual = true; }  // adapt_note
 
   // ---- items dropped by the stage that is about to recompute them (and by the events)
   void drop_scores() { scores = adapt_pending = adapt_bad_qual = adapt_sampled = apply_recs_valid = false; }
-  void drop_sorted() { sorted = sorted_qname = false; }
+  void drop_sorted() { sorted = sorted_qname = sorted_keep = sorted_keep_by_split = false; }
   void drop_marked() { marked = false; }
   void drop_qual_hint() { have_qual_present = false; }
   void drop_presort() { presorted = false; }
@@ -88,7 +95,7 @@ struct Derived {
   void fixed_fields_changed() { drop_keys(); drop_scores(); drop_sorted(); drop_marked(); }  // MAPQ / CIGAR / has_sr: elp_clean_sam, elp_filter_records
   void qual_changed() { drop_scores(); drop_qual_hint(); }                                    // elp_bqsr_apply.  NOT the keys
   void flag_qual_restored() { fixed_fields_changed(); drop_qual_hint(); }                     // elp_rollback
-  void split_changed() { drop_marked(); }                                                     // elp_split_classify
+  void split_changed() { drop_marked(); if (sorted_keep_by_split) drop_sorted(); }            // elp_split_classify (a keep permutation by split was made from the ids)
   void duplicate_bit_cleared() { drop_sorted(); drop_marked(); }                              // elp_clear_duplicate_flag.  NOT keys / scores
   void dictionary_replaced() { fixed_fields_changed(); header_changed(); have_snapshot = false; }  // elp_replace_reference_dictionary: REFID, RNEXT, has_sr, n_ref
   void radix_timed_out() { drop_sorted(); drop_marked(); }                                    // fetch_err: whichever sort it was, its result is wrong

@@ -267,11 +267,30 @@ int merge_refuses_queryname(elp_ctx *groups, const char *who) {
                    "files is not implemented (cmd/merge.go:175-176)", who);
 }
 
-// MergeSortedFilesSplitPerChromosome's order as ranks, on the device: slots[j] = output slot of the j-th record of `spread`'s sorted output
-// among `groups`' sorted output (scratch slot 5 of `groups`; valid until that slot is reused).  Queued on groups->stream.
+// keys[0 .. n_out) of a keep-ordered context must be non-decreasing for the merge's binary search: (refid, POS) ascending, refid -1 (the
+// high word 0xFFFFFFFF) last - what a file with SO:coordinate in its header holds.  *bad |= 1 if entry k is smaller than entry k - 1.
+// MERGE_CHECK_W entries per workgroup; the first entry of a workgroup looks at the last of the one in front.
+constexpr uint32_t MERGE_CHECK_W = 256;
+__global__ __launch_bounds__(MERGE_CHECK_W) void k_merge_check_order(uint64_t n_out, const uint64_t *__restrict__ keys, uint32_t *__restrict__ bad) {
+  const uint64_t k = (uint64_t)blockIdx.x * MERGE_CHECK_W + threadIdx.x;
+  const bool inv = k > 0 && k < n_out && keys[k] < keys[k - 1];
+  if (__ballot(inv) && (threadIdx.x & 63u) == 0) atomicOr(bad, 1u);
+}
+
+// MergeSortedFilesSplitPerChromosome's order as ranks, on the device: slots[j] = output slot of the j-th record of `spread`'s output
+// among `groups`' output (scratch slot 5 of `groups`; valid until that slot is reused).  Queued on groups->stream.
+// Either context holds a coordinate permutation or a plain keep permutation (elp_order_keep, by_split = 0): by choosing this call for
+// keep-ordered contexts the host vouches for SO:coordinate, as cmd/merge.go:157-174 chooses by header.HDSO() - a context that received
+// its records in file order (contigs in refid order, `*` last) then holds them in the merge's order.  The keys of a keep-ordered side
+// are checked (one pass, one word read back): an inversion is ELP_ERR_DATA, where the reference would write some order of its own.
 int merge_spread_slots(elp_ctx *groups, elp_ctx *spread, uint64_t **slots_out) {
   if (groups->derived.sorted_qname || spread->derived.sorted_qname) return merge_refuses_queryname(groups, "elp_merge_spread");
-  if (!groups->derived.sorted || !spread->derived.sorted) return set_error(groups, ELP_ERR_ARG, "elp_merge_spread: both contexts must be coordinate-sorted");
+  if (!groups->derived.sorted || !spread->derived.sorted)
+    return set_error(groups, ELP_ERR_ARG, "elp_merge_spread: both contexts must be coordinate-sorted (elp_sort_coordinate) or hold coordinate-sorted input in "
+                     "input order (elp_order_keep with by_split = 0)");
+  if (groups->derived.sorted_keep_by_split || spread->derived.sorted_keep_by_split)
+    return set_error(groups, ELP_ERR_ARG, "elp_merge_spread: a context holds a keep permutation ordered by split id (elp_order_keep with by_split != 0): "
+                     "the coordinate merge takes plain input order only");
   if (groups->device != spread->device) return set_error(groups, ELP_ERR_ARG, "elp_merge_spread: contexts on different devices");
   ELP_HIP(groups, hipSetDevice(groups->device));
   // (a sort defers the read of its radix passes' look-back timeout bit: nothing is merged from a permutation that was flagged wrong)
@@ -280,20 +299,34 @@ int merge_spread_slots(elp_ctx *groups, elp_ctx *spread, uint64_t **slots_out) {
   // the mapped part of the groups' output (the unmapped split is appended behind the merge, :560-576)
   const uint64_t ns = spread->n - spread->n_sr;
   uint64_t *kg, *ks, *slots;
-  ELP_TRY(scratch(groups, 5, (groups->n + 8) + 2 * (ns + 8), &kg));
+  ELP_TRY(scratch(groups, 5, (groups->n + 8) + 2 * (ns + 8) + 2, &kg));
   ks = kg + groups->n + 8;
   slots = ks + ns + 8;
+  uint32_t *bad = reinterpret_cast<uint32_t *>(slots + ns + 8);
   const uint64_t ng_all = groups->n - groups->n_sr;
+  const bool check_g = groups->derived.sorted_keep && ng_all > 1, check_s = spread->derived.sorted_keep && ns > 1;
   ELP_HIP(groups, elp::stream_wait(spread->stream));
+  if (check_g || check_s) ELP_HIP(groups, hipMemsetAsync(bad, 0, 4, groups->stream));
   if (ng_all)
     ELP_LAUNCH(groups, "merge_keys", k_perm_keys, dim3(blocks_for(ng_all, 256)), dim3(256), 0, ng_all, (const uint32_t *)groups->perm.p,
                (const int32_t *)groups->refid.p, (const int32_t *)groups->pos.p, kg);
-  if (ns) {
+  if (ns)
     ELP_LAUNCH(groups, "merge_keys", k_perm_keys, dim3(blocks_for(ns, 256)), dim3(256), 0, ns, (const uint32_t *)spread->perm.p,
                (const int32_t *)spread->refid.p, (const int32_t *)spread->pos.p, ks);
-    // unmapped reads (refid -1 -> 0xFFFFFFFF........) sort behind every contig: the search covers them without a special case
-    ELP_LAUNCH(groups, "merge_rank", k_merge_rank, dim3(blocks_for(ns, 256)), dim3(256), 0, ng_all, (const uint64_t *)kg, ns, (const uint64_t *)ks, slots);
+  if (check_g)
+    ELP_LAUNCH(groups, "merge_check_order", k_merge_check_order, dim3(blocks_for(ng_all, MERGE_CHECK_W)), dim3(MERGE_CHECK_W), 0, ng_all, (const uint64_t *)kg, bad);
+  if (check_s)
+    ELP_LAUNCH(groups, "merge_check_order", k_merge_check_order, dim3(blocks_for(ns, MERGE_CHECK_W)), dim3(MERGE_CHECK_W), 0, ns, (const uint64_t *)ks, bad);
+  if (check_g || check_s) {
+    uint32_t h_bad = 0;
+    ELP_HIP(groups, hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, groups->stream));
+    ELP_HIP(groups, elp::stream_wait(groups->stream));
+    if (h_bad)
+      return set_error(groups, ELP_ERR_DATA, "elp_merge_spread: records are not in coordinate order ((refid, POS) must not decrease in a context that holds "
+                       "its input order, elp_order_keep; sort it with elp_sort_coordinate instead)");
   }
+  // unmapped reads (refid -1 -> 0xFFFFFFFF........) sort behind every contig: the search covers them without a special case
+  if (ns) ELP_LAUNCH(groups, "merge_rank", k_merge_rank, dim3(blocks_for(ns, 256)), dim3(256), 0, ng_all, (const uint64_t *)kg, ns, (const uint64_t *)ks, slots);
   *slots_out = slots;
   return 0;
 }

@@ -4,6 +4,7 @@
 
     Engine.sort_coordinate   ~ sam.By(sam.CoordinateLess).ParallelStableSort        (sam/sam-types.go:639)
     Engine.sort_queryname    ~ sam.By(sam.QNAMELess).ParallelStableSort             (sam/filter-pipeline.go:118-122)
+    Engine.order_keep        ~ StrictOrd(Slice(&alns)): no sort, input order         (sam/filter-pipeline.go:110-112)
     Engine.mark_duplicates   ~ filters.MarkDuplicates(alsoOpticals)                 (filters/mark-duplicates.go:406)
     Engine.dup_metrics       ~ filters.MarkOpticalDuplicates(reads, pairs, dist)    (filters/mark-optical-duplicates.go:469)
     Engine.recalibrate       ~ (*BaseRecalibrator).Recalibrate(reads, maxCycle)     (filters/bqsr.go:467)
@@ -197,13 +198,30 @@ class Engine:
         bgzf = np.ascontiguousarray(bgzf, dtype=np.uint8)
         self._check(self.L.elp_stage_bgzf(self.h, _vp(bgzf), bgzf.size, first_record, split_id))
 
-    def emit_merged_bam(self, spread: "Engine") -> np.ndarray:
-        """this context's (group splits) and `spread`'s sorted outputs as one BAM record stream in the merge's order (elp_emit_merged_bam)"""
+    def _emit_two(self, fn, spread: "Engine") -> np.ndarray:
         n = C.c_uint64()
-        self._check(self.L.elp_emit_merged_bam(self.h, spread.h, C.c_void_p(0), 0, C.byref(n)))
+        self._check(fn(self.h, spread.h, C.c_void_p(0), 0, C.byref(n)))
         out = np.empty(int(n.value), dtype=np.uint8)
-        self._check(self.L.elp_emit_merged_bam(self.h, spread.h, _vp(out), out.size, C.byref(n)))
+        self._check(fn(self.h, spread.h, _vp(out), out.size, C.byref(n)))
         return out[:int(n.value)]
+
+    def emit_merged_bam(self, spread: "Engine") -> np.ndarray:
+        """this context's (group splits) and `spread`'s outputs - coordinate-sorted, or sorted input in input order (order_keep) - as one BAM
+        record stream in the merge's order (elp_emit_merged_bam)"""
+        return self._emit_two(self.L.elp_emit_merged_bam, spread)
+
+    def emit_merged_bgzf(self, spread: "Engine") -> np.ndarray:
+        """emit_merged_bam's stream as BGZF members (elp_emit_merged_bgzf); the size query gives an upper bound, the call the actual size"""
+        return self._emit_two(self.L.elp_emit_merged_bgzf, spread)
+
+    def emit_concat_bam(self, spread: "Engine") -> np.ndarray:
+        """the merge of unsorted splits (elp_emit_concat_bam): this context's split 0, all of `spread`, this context's splits 1, 2, ... -
+        each in input order.  This context holds order_keep(by_split=True), `spread` order_keep()"""
+        return self._emit_two(self.L.elp_emit_concat_bam, spread)
+
+    def emit_concat_bgzf(self, spread: "Engine") -> np.ndarray:
+        """emit_concat_bam's stream as BGZF members (elp_emit_concat_bgzf)"""
+        return self._emit_two(self.L.elp_emit_concat_bgzf, spread)
 
     # ---- fused predicates, split / merge bookkeeping (include/elprep_hip.h)
     def filter_records(self, remove_unmapped=False, remove_unmapped_strict=False, min_mapq=0, remove_non_exact=False, remove_duplicates=False,
@@ -366,6 +384,12 @@ class Engine:
     def sort_queryname(self, fetch: bool = True) -> Optional[np.ndarray]:
         """elp_sort_queryname: QNAME order (Go string order), ties in staging order, records that are not output behind the others"""
         self._check(self.L.elp_sort_queryname(self.h))
+        return self.permutation() if fetch else None
+
+    def order_keep(self, by_split: bool = False, fetch: bool = True) -> Optional[np.ndarray]:
+        """elp_order_keep: the permutation of a run that does not sort (--sorting-order keep / unknown / unsorted) - the records that are
+        output in staging order, the others behind them; by_split: both parts ordered by split id first"""
+        self._check(self.L.elp_order_keep(self.h, 1 if by_split else 0))
         return self.permutation() if fetch else None
 
     def permutation(self) -> np.ndarray:

@@ -269,25 +269,36 @@ def route_device(reader, b: Batch, group_of_ref: np.ndarray, n_groups: int, owne
     return dst_local.n - n0, dst_spread.n - n1
 
 
-def emit_merged_device(groups, spread, part, group_of_ref: np.ndarray, n_groups: int, owner: np.ndarray, rank: int, world: int) -> np.ndarray:
+def _order_call(e, order: str):
+    """the call that makes a context's permutation: order = "coordinate" (elp_sort_coordinate) or "keep" (elp_order_keep: the input is sorted
+    already, effectiveSortingOrder turned the request into Keep, sam/filter-pipeline.go:208-225)"""
+    if order not in ("coordinate", "keep"):
+        raise ValueError("order must be 'coordinate' or 'keep', not %r" % (order,))
+    return e.sort_coordinate if order == "coordinate" else (lambda fetch=True: e.order_keep(False, fetch))
+
+
+def emit_merged_device(groups, spread, part, group_of_ref: np.ndarray, n_groups: int, owner: np.ndarray, rank: int, world: int,
+                       order: str = "coordinate") -> np.ndarray:
     """The merge phase across ranks through the C ABI (MergeSortedFilesSplitPerChromosome, sam/split-merge.go:410-576): the spread split's
     owner sends every rank the spread reads of that rank's contig groups - in the spread file's coordinate order, with the FLAG and QUAL
     columns as the path left them (elp_exchange_records; elp_copy_records for its own) - into the rank's `part` context; every rank then
     emits the merge of its group splits' sorted output and those reads as one stream of BAM records (elp_emit_merged_bam: the spread
     reads behind the group reads of their position, the rank's unmapped split last).  The output file is the ranks' streams cut at
     their group boundaries in @SQ order + the unmapped split.  `groups` and `spread` are coordinate-sorted and hold the inflated BAM
-    records (elp_stage_bam); `spread` is empty on every rank but the owner; `part` is an empty context of the same device group."""
+    records (elp_stage_bam); `spread` is empty on every rank but the owner; `part` is an empty context of the same device group.
+    order = "keep": `groups` and `spread` hold sorted input in input order (order_keep); `part`, which receives its reads in the spread
+    file's order, is ordered the same way."""
     spread_owner = int(owner[n_groups + 1])
     part.reset()
     if rank == spread_owner and spread.n:
         split, _, _ = spread.split_classify(group_of_ref, n_groups)   # the contig group of every spread read
-        order = spread.permutation()[:spread.n_sorted]
-        dest = owner[split[order]]
+        sorder = spread.permutation()[:spread.n_sorted]  # the spread file's output order
+        dest = owner[split[sorder]]
     else:
-        order, dest = np.zeros(0, np.uint32), np.zeros(0, np.int32)
+        sorder, dest = np.zeros(0, np.uint32), np.zeros(0, np.int32)
     for s in range(world):
         sp, rp = (rank + s) % world, (rank - s + world) % world
-        idx = order[dest == sp].astype(np.uint32) if rank == spread_owner else np.zeros(0, np.uint32)
+        idx = sorder[dest == sp].astype(np.uint32) if rank == spread_owner else np.zeros(0, np.uint32)
         if s == 0:
             if idx.size:
                 part.copy_records_from(spread, idx, new_split=0)
@@ -296,7 +307,7 @@ def emit_merged_device(groups, spread, part, group_of_ref: np.ndarray, n_groups:
             recv_from = rp if rp == spread_owner else -1
             if send_to >= 0 or recv_from >= 0:
                 (spread if rank == spread_owner else part).exchange_records(send_to, idx, part if recv_from >= 0 else None, recv_from, new_split=0)
-    part.sort_coordinate(fetch=False)
+    _order_call(part, order)(False)
     return groups.emit_merged_bam(part)
 
 
@@ -341,6 +352,13 @@ def merge_splits(groups: List[Batch], spread: Batch, unmapped: Batch) -> Batch:
     both = Batch.concat([cat, spread])
     idx = np.where(code >= 0, code, cat.n + (-code - 1))
     return Batch.concat([both.take(idx), unmapped])
+
+
+def merge_splits_unsorted(groups: List[Batch], spread: Batch, unmapped: Batch) -> Batch:
+    """(Test infrastructure: the product concatenates on the device - elp_emit_concat_bam.)  MergeUnsortedFilesSplitPerChromosome on
+    payloads (sam/split-merge.go:581-619), what `elprep merge` does for a header that is neither SO:coordinate nor SO:queryname
+    (cmd/merge.go:178-188): the unmapped file, then the spread file, then the group files in index order, each in its own order."""
+    return Batch.concat([unmapped, spread] + list(groups))
 
 
 # ------------------------------------------------------------------------------------------------ per-rank driver
@@ -437,13 +455,14 @@ class SfmRank:
         for e in self.engines:
             e.sync()
 
-    def gather(self, max_cycle: int, pixel_dist: int = 100):
-        """mark duplicates + sort + duplication metrics + BQSR tables of every split of this rank, then THE all-reduce."""
+    def gather(self, max_cycle: int, pixel_dist: int = 100, order: str = "coordinate"):
+        """mark duplicates + sort (order = "keep": order_keep in its place) + duplication metrics + BQSR tables of every split of this
+        rank, then THE all-reduce."""
         if self.collective == "torch":
             tot = None
             for e in self.engines:
                 e.mark_duplicates(True, fetch=False)
-                e.sort_coordinate(fetch=False)  # the sort is the Finalize step behind the filters (sam/filter-pipeline.go:116)
+                _order_call(e, order)(False)  # the sort is the Finalize step behind the filters (sam/filter-pipeline.go:116)
                 ctr = e.dup_metrics(pixel_dist)
                 qt, ct, xt = e.recalibrate(max_cycle)
                 flat = np.concatenate([qt.ravel(), ct.ravel(), xt.ravel(), ctr.ravel()])
@@ -461,7 +480,7 @@ class SfmRank:
         ctr = None
         for e in self.engines:
             e.mark_duplicates(True, fetch=False)
-            e.sort_coordinate(fetch=False)
+            _order_call(e, order)(False)
             c7 = e.dup_metrics(pixel_dist)
             ctr = c7 if ctr is None else ctr + c7
             e.recalibrate_device(max_cycle)  # tables stay in HBM
@@ -474,7 +493,7 @@ class SfmRank:
         qt, ct, xt = e0.tables_fetch(reuse=True)
         return qt, ct, xt, ctr
 
-    def step(self, max_cycle: int, pixel_dist: int, host_pool, finalize, finalize_rows=None):
+    def step(self, max_cycle: int, pixel_dist: int, host_pool, finalize, finalize_rows=None, order: str = "coordinate"):
         """One pass of the path over this rank's splits with the host's float64 finalisation hidden behind the sorts, as the one-context
         filter step has it: mark duplicates, duplication metrics (order-independent sums: they do not need the sort) and the BQSR count of
         every split, THE all-reduce (tables + counters), then the tables' way to the host, FinalizeBQSRTables and the LUT's upload to both
@@ -482,9 +501,11 @@ class SfmRank:
         `finalize_rows(quals, q_rows, c_rows, x_rows) -> (rows, defaults, present)` (optional): the tables and the LUT in ROWS form - only the
         rows of the qualities this rank's contexts counted cross PCIe (Engine.tables_fetch_rows / lut_upload_rows); if another rank
         counted a quality this one did not, the all-reduced tables hold a row outside that set and the dense forms are taken.
-        Returns the all-reduced duplication counters."""
+        order = "keep": the input is sorted already (a header with SO:coordinate) - order_keep takes the place of sort_coordinate on both
+        contexts, on the same pool threads.  Returns the all-reduced duplication counters."""
+        _order_call(self.engines[0], order)  # (the argument check, in front of any work)
         if self.collective == "torch":
-            qt, ct, xt, ctr = self.gather(max_cycle, pixel_dist)
+            qt, ct, xt, ctr = self.gather(max_cycle, pixel_dist, order)
             lut, present = finalize(qt, ct, xt)
             self.apply(lut, present, max_cycle)
             return ctr
@@ -502,7 +523,7 @@ class SfmRank:
                 # round 6: behind mark duplicates the coordinate sort, the metrics pass and the BQSR count need nothing of each other; the
                 # library runs the first two on side lanes of the context (streams and scratch of their own), a host thread each drives them
                 # under the gather's kernels
-                st = sort_pool.submit(e.sort_coordinate, False)
+                st = sort_pool.submit(_order_call(e, order), False)
                 mx = pool.submit(e.dup_metrics, pixel_dist)
                 e.recalibrate_device(max_cycle)  # tables stay in HBM
                 c7 = mx.result()
@@ -540,7 +561,7 @@ class SfmRank:
                 e1.lut_upload(lut, present, max_cycle)
             return lut, present
         fin = host_pool.submit(host_side)
-        side = self._side.submit(lambda: e1.sort_coordinate(fetch=False)) if self.n[1] else None
+        side = self._side.submit(_order_call(e1, order), False) if self.n[1] else None
         if side is not None:
             side.result()
         fin.result()
@@ -555,10 +576,11 @@ class SfmRank:
         for e in self.engines:
             e.apply_bqsr(lut, present, max_cycle, fetch=False)
 
-    def emit_merged(self, group_of_ref: np.ndarray, n_groups: int, owner: np.ndarray) -> np.ndarray:
+    def emit_merged(self, group_of_ref: np.ndarray, n_groups: int, owner: np.ndarray, order: str = "coordinate") -> np.ndarray:
         """the merge phase of this rank (emit_merged_device): the BAM records of its contig groups' output with the spread reads of those
         groups inserted - every context of the rank that sends or receives joins the device group first (the communicator the tables were
-        reduced on, or the send-receive callback).  The records must have been staged from BAM bytes (route(..., stage=...))."""
+        reduced on, or the send-receive callback).  The records must have been staged from BAM bytes (route(..., stage=...)).  order: what
+        step() was given."""
         from .engine import Engine
         if getattr(self, "_part", None) is None:
             self._part = Engine(self.header, self._device_ordinal)
@@ -571,7 +593,7 @@ class SfmRank:
                     else:
                         e.group_init_transport(self.comm.rank, self.comm.world, lambda v: None)
                         e.group_set_p2p(self.comm.sendrecv)
-        return emit_merged_device(self.engines[0], self.engines[1], self._part, group_of_ref, n_groups, owner, self.comm.rank, self.comm.world)
+        return emit_merged_device(self.engines[0], self.engines[1], self._part, group_of_ref, n_groups, owner, self.comm.rank, self.comm.world, order)
 
     def close(self):
         if self._side is not None:

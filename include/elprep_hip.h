@@ -129,7 +129,8 @@ uint64_t elp_num_qual_bytes(const elp_ctx *ctx);     /* size of the staged QUAL 
  *   a BAM reader knows them; without them the call walks the block_size chain on the host (one dependent load per record).
  *   Fast path: `bytes` in page-locked memory (elp_pinned_alloc) - the DMA engine reads it in place;
  *   pageable memory goes through a pinned double buffer.  Returns when `bytes` may be reused.
- * elp_emit_sorted_bam: formatBamAlignment (:635-737) of the elp_num_sorted() records of the sort's output, in that order, into
+ * elp_emit_sorted_bam: formatBamAlignment (:635-737) of the elp_num_sorted() records of the context's permutation - made by
+ *   elp_sort_coordinate, elp_sort_queryname or elp_order_keep, whichever ran last - in that order, into
  *   `out` (host memory, `cap` bytes; NULL = just compute *n_bytes_out): FLAG and QUAL as the path left them, bin() recomputed
  *   (:443-468), optional fields re-encoded as formatBamTag does (:481-632).  BGZF deflate stays with the host. */
 int elp_set_read_group_ids(elp_ctx *ctx, const char *const *ids);
@@ -161,8 +162,27 @@ int elp_stage_bgzf(elp_ctx *ctx, const uint8_t *bgzf, uint64_t n_bytes, uint64_t
 int elp_emit_sorted_bgzf(elp_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out);
 /* The merge of `elprep merge` / `sfm` phase 3 with payloads (MergeSortedFilesSplitPerChromosome, sam/split-merge.go:410-576): the sorted
  * outputs of a context that holds group splits and of the context that holds the spread split as ONE stream of BAM records in the merge's
- * order (elp_merge_spread's slots), gathered in HBM.  Both contexts staged with elp_stage_bam, coordinate-sorted, on one device. */
+ * order (elp_merge_spread's slots), gathered in HBM.  Both contexts staged with elp_stage_bam, on one device, each coordinate-sorted
+ * (elp_sort_coordinate) or holding coordinate-sorted input in input order (elp_order_keep with by_split = 0; elp_merge_spread states the
+ * rule and its check).
+ * elp_emit_merged_bgzf: the same stream as BGZF members, as elp_emit_sorted_bgzf writes the sorted one (`sfm`'s final output): members of
+ *   65280 payload bytes except the last, wherever the device passes fall (the bytes behind a pass's last full member are carried into the
+ *   next pass); inflating the members gives elp_emit_merged_bam's bytes; a size query (out = NULL) returns the stored form's size, an
+ *   upper bound and the room `out` must offer.  Same checks and errors as elp_emit_merged_bam. */
 int elp_emit_merged_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out);
+int elp_emit_merged_bgzf(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out);
+/* The merge of UNSORTED splits: MergeUnsortedFilesSplitPerChromosome (sam/split-merge.go:581-619), which `elprep merge` takes for every
+ * header that says neither SO:coordinate nor SO:queryname (cmd/merge.go:178-188).  The stream is (1) the output records of `groups` with
+ * split id 0 - the unmapped file -, (2) all output records of `spread`, (3) the output records of `groups` with split ids 1, 2, ... in
+ * id order - the group files; every part in staging order; records that are not output (sr-tagged copies, rejected records) appear
+ * nowhere.  `groups` must hold a keep permutation made with by_split = 1 and `spread` one made with by_split = 0 (elp_order_keep), else
+ * ELP_ERR_ARG; `spread` may be an empty context.  Otherwise the checks of elp_emit_merged_bam: one device, both staged with elp_stage_bam,
+ * equal tag filters, equal replacing read groups, equal dictionary-replacement state (ELP_ERR_ARG), fewer than 2^31 output records
+ * (ELP_ERR_UNSUPPORTED).  Ordering the stream across ranks is the host's: a rank's call covers the splits its context holds.
+ * Reads: both permutations, the split-id column of `groups` (the end of the unmapped file among its output: one word made on the
+ * device), and what elp_emit_sorted_bam reads.  Writes: `out` only.  elp_emit_concat_bgzf is the BGZF form, as elp_emit_merged_bgzf. */
+int elp_emit_concat_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out);
+int elp_emit_concat_bgzf(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out);
 
 /* ---- the options that touch a record's optional fields (filters/simple-filters.go; cmd/filter.go:696-902) ----
  * The settings of elp_set_tag_filter and elp_set_replace_read_group belong to a run: elp_reset and elp_set_header clear both.
@@ -176,7 +196,7 @@ int elp_emit_merged_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t
  *   (utils/small-map.go:89-99): a field goes out iff its key is not in the remove list (and remove is not `all`) and, with a keep
  *   filter, its key is in the keep list; fields of one key are all treated alike, the survivors keep their order and are re-encoded as
  *   before.  Call any time before the emit call (n_remove = 0, n_keep = -1 takes the filter away).  It acts on elp_emit_sorted_bam,
- *   elp_emit_sorted_bgzf and elp_emit_merged_bam - sizes, offsets, block_size, the size query, BGZF framing; the merged stream takes the
+ *   elp_emit_sorted_bgzf, elp_emit_merged_bam / _bgzf and elp_emit_concat_bam / _bgzf - sizes, offsets, block_size, the size query, BGZF framing; the merged stream takes the
  *   filter of `groups` and the call returns ELP_ERR_ARG if `spread`'s differs.  Nothing else sees it (filters2 runs behind ApplyBQSR,
  *   cmd/filter.go:66-100): the staged rgid column and sr states, duplicate marking, BQSR, elp_copy_records and elp_exchange_records work
  *   on the unfiltered records; removing RG from the output changes no table.  Malformed fields and H fields are reported as without a
@@ -273,9 +293,18 @@ int elp_filter_records_flat(elp_ctx *ctx, int remove_unmapped, int remove_unmapp
  *   spread file (mate in another group); counts_out[n_groups + 2] = records per split (unmapped, groups, spread).  The split ids are
  *   also written to the context's split-id column (elp_batch.split), so that elp_copy_records / elp_exchange_records with new_split = -1
  *   deliver every record with the id of its split file.
- * elp_merge_spread: MergeSortedFilesSplitPerChromosome (:410-576) as ranks: both contexts coordinate-sorted; slot_of_spread_out[j] =
- *   output slot of the j-th record of `spread`'s sorted output among `groups`' sorted output (behind every group read of its
- *   (refid, POS) and in front of the first greater one; group reads fill the remaining slots in order). */
+ * elp_merge_spread: MergeSortedFilesSplitPerChromosome (:410-576) as ranks: slot_of_spread_out[j] = output slot of the j-th record of
+ *   `spread`'s output among `groups`' output (behind every group read of its (refid, POS) and in front of the first greater one; group
+ *   reads fill the remaining slots in order).  Each context holds a coordinate permutation (elp_sort_coordinate) or a plain keep
+ *   permutation (elp_order_keep with by_split = 0); one of each is allowed, both are (refid, POS)-sorted streams.  A keep permutation is
+ *   the sorted-input case: `sfm` on a header with SO:coordinate filters every split in input order (effectiveSortingOrder,
+ *   sam/filter-pipeline.go:208-225) and interleaves the spread reads by (refid, POS).  By choosing this call the host vouches for
+ *   SO:coordinate, as cmd/merge.go:157-174 chooses by header.HDSO(); a context that received its split files in file order holds them in
+ *   the merge's order (the group files are read contig by contig in refid order, the groups hold consecutive contigs, `*` records are a
+ *   sorted file's tail and are appended last, :557-576).  The merge's binary search needs (refid, POS) non-decreasing with refid -1 last:
+ *   every keep-ordered side is checked (one pass over its keys, one word read back) and a violation returns ELP_ERR_DATA "records are
+ *   not in coordinate order" with nothing emitted - a stated limit: the reference would write some order of its own.  A queryname
+ *   permutation returns ELP_ERR_UNSUPPORTED, a keep permutation made with by_split != 0 ELP_ERR_ARG, no permutation ELP_ERR_ARG. */
 int elp_split_classify(elp_ctx *ctx, const int32_t *group_of_ref, int32_t n_groups, uint16_t *split_out, uint8_t *spread_out, uint64_t *counts_out);
 /* elp_copy_records: the write side of the same routing (:280-293 writes the record into the file of its split, and a copy tagged sr:i:1
  *   into the group file if the original goes to the spread file): appends the records idx[0 .. n) of `src` (staging indices, any order)
@@ -314,6 +343,8 @@ int elp_sort_coordinate(elp_ctx *ctx);
  * where the gather follows mark duplicates at once: no gain - the GPU is busy either way, profiles/round6_sort_ahead_ab.txt; it is for a
  * host that has work of its own between the two calls.) */
 int elp_sort_ahead(elp_ctx *ctx, int on);
+/* the permutation the context holds - made by elp_sort_coordinate, elp_sort_queryname or elp_order_keep, whichever ran last;
+ * ELP_ERR_ARG if none of them has run since the staged records last changed */
 int elp_get_permutation(elp_ctx *ctx, uint32_t *perm_out /* n */);
 /* ---- queryname sort: By(QNAMELess).ParallelStableSort (sam/filter-pipeline.go:118-122, sam/sam-types.go:475-481, :639-641) ----
  * The Finalize step of `elprep filter / sfm --sorting-order queryname` (cmd/filter.go:361,451), in place of elp_sort_coordinate.
@@ -323,7 +354,7 @@ int elp_get_permutation(elp_ctx *ctx, uint32_t *perm_out /* n */);
  * records that are not output (sr-tagged copies, records rejected by elp_filter_records) follow behind them, ALSO in QNAME order with
  * ties in staging order.  Reads the QNAME column and the record-state column only (no sort keys, no scores: nothing of
  * elp_mark_duplicates is needed), so it may be called on its own or after elp_mark_duplicates, elp_filter_records or
- * elp_sort_coordinate, with the same result.  The context remembers which sort made its permutation last: elp_get_permutation and
+ * elp_sort_coordinate or elp_order_keep, with the same result.  The context remembers which call made its permutation last: elp_get_permutation and
  * elp_emit_sorted_bam / elp_emit_sorted_bgzf give that order; elp_merge_spread and elp_emit_merged_bam return ELP_ERR_UNSUPPORTED
  * while either context holds a queryname permutation (the reference panics: "Merging of files sorted by queryname not yet
  * implemented.", cmd/merge.go:175-176).  Key passes queued ahead for a coordinate sort (elp_sort_ahead) are left as they are.
@@ -334,8 +365,36 @@ int elp_get_permutation(elp_ctx *ctx, uint32_t *perm_out /* n */);
  * validity items "sorted" / "sorted_qname" (csrc/derived.hpp), nothing else of the context.  Limits as for staging: 2^32-16 records,
  * QNAMEs of at most 1000 bytes. */
 int elp_sort_queryname(elp_ctx *ctx);
+/* ---- no sort: `--sorting-order keep` (the default, cmd/filter.go:451), `unknown`, `unsorted` ----
+ * The permutation of a run that does not sort.  Sam.AddNodes collects the alignments with StrictOrd(Slice) - input order - for Keep and
+ * Unknown (sam/filter-pipeline.go:110-112) and with Seq(Slice), of which input order is one legal result, for Unsorted (:123-124);
+ * effectiveSortingOrder (:208-225) turns a requested `coordinate` into Keep whenever the input header already says SO:coordinate - the
+ * production case of a BAM the aligner's pipeline has sorted, which the reference writes in the order it came (a file sorted by
+ * (refid, POS) alone is NOT in CoordinateLess's nine-key order: elp_sort_coordinate would reorder records the reference leaves alone).
+ * The host's choice after effectiveSortingOrder: Keep / Unknown / Unsorted -> elp_order_keep, Coordinate -> elp_sort_coordinate,
+ * Queryname -> elp_sort_queryname.
+ * perm[0 .. elp_num_sorted()) = the records that are output (state 0 in the record-state column), perm[elp_num_sorted() .. n) = the
+ * records that are not (sr-tagged copies, records rejected by elp_filter_records, elp_filter_exact_strict or
+ * elp_replace_reference_dictionary).  by_split == 0: both parts in staging order.  by_split != 0: both parts ordered by split id
+ * ascending (the split column, ids 0 .. 65535) with staging order inside a split: a context that holds several `elprep split` files
+ * delivers them file after file (elp_emit_concat_bam wants this form of its groups context).
+ * Reads: the record-state column, and the split-id column if by_split.  Writes: the permutation and its validity items "sorted",
+ * "sorted_keep", "sorted_keep_by_split" (csrc/derived.hpp).  Nothing else is needed - no keys, no scores, no marks: call it on its own
+ * or after any operator; n == 0 succeeds.  It replaces whatever permutation the context held, and a later elp_sort_coordinate or
+ * elp_sort_queryname replaces it in turn; elp_get_permutation, elp_emit_sorted_bam and elp_emit_sorted_bgzf take it as any other (sizes,
+ * the size query, BGZF framing, the tag filter and elp_set_replace_read_group act as before).  Every change to the staged records that
+ * invalidates a sort's permutation invalidates this one; elp_split_classify invalidates it only if it was made with by_split != 0 (it
+ * rewrites the column that order was made from).
+ * Concurrency: as elp_sort_coordinate - the call runs on the same side lane of the context (a stream, scratch pool and error words of
+ * its own) and writes the permutation only; once elp_mark_duplicates has returned, a host may call it from a thread of its own WHILE
+ * other threads call elp_dup_metrics and drive elp_bqsr_gather(_device) -> finalize -> elp_bqsr_apply on the same context.  Calls that
+ * CHANGE staged records must not overlap with it.  Key passes queued ahead for a coordinate sort (elp_sort_ahead) are left as they are.
+ * Cost: by_split == 0 is a two-pass partition, about 6 bytes per record (the state byte twice, the permutation once); by_split != 0
+ * is a stable radix sort of ceil((bits(max split id) + 1) / 8) passes and takes the by_split == 0 path when every split id is 0.
+ * Errors: ELP_ERR_ARG for a NULL context, ELP_ERR_UNSUPPORTED for more than 2^32-16 records. */
+int elp_order_keep(elp_ctx *ctx, int by_split);
 /* number of records that survive RemoveOptionalReads = staged records without the sr tag: the first elp_num_sorted() entries of
- * the permutation are the output of the run, the tagged copies follow behind them */
+ * the permutation (of either sort, or of elp_order_keep) are the output of the run, the tagged copies follow behind them */
 uint64_t elp_num_sorted(const elp_ctx *ctx);
 
 /* ---- mark duplicates: filters.MarkDuplicates (filters/mark-duplicates.go:398-445) ----
