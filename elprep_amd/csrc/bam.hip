@@ -16,6 +16,7 @@
 
 #include "common.hpp"
 #include "bamtag.hpp"
+#include "bamout.hpp"
 
 namespace elp {
 
@@ -140,25 +141,7 @@ __global__ __launch_bounds__(256) void k_bam_payload(BamPay m) {
 }
 
 // ---------------------------------------------------------------- out
-struct BamOut {
-  uint64_t n_out;
-  const uint32_t *perm;
-  const uint8_t *raw;
-  const uint64_t *raw_off;   // per staged record: offset of its BAM record in raw (n + 1)
-  const int32_t *refid, *pos, *next_refid, *pnext, *tlen;
-  const uint16_t *flag;
-  const uint8_t *mapq;
-  const uint32_t *l_seq;
-  const uint64_t *qname_off, *cigar_off, *qual_off;
-  const uint8_t *qname, *qual;
-  const uint32_t *cigar;
-  const uint32_t *drop;      // elp_set_tag_filter: bit k = fields with the 16-bit key k stay behind (65536 bits); nullptr = no filter
-  const uint8_t *rg_new;     // elp_set_replace_read_group: the id every record goes out with (rg_on), rg_len bytes
-  uint32_t rg_len, rg_on;
-};
-constexpr uint32_t KEY_RG = tag_key_of('R', 'G');
-// filters2's RemoveOptionalFields / KeepOptionalFields (filters/simple-filters.go:235-288) as one look-up: every field of a key goes or stays
-__device__ __forceinline__ bool tag_dropped(const uint32_t *__restrict__ drop, uint32_t key) { return drop && ((drop[key >> 5] >> (key & 31)) & 1u); }
+// (BamOut, tag_dropped, out_source: bamout.hpp - sam.hip writes SAM text from the same columns)
 // size of output record k (block_size field included); *tags_at = offset of the tags inside the input record
 // OPT: a tag filter or a replacing read group is set.  The walks are bound by their chain of dependent loads and the per-field tests cost
 // the emitter 8 % where nothing is set (measured), so a context without either runs the instantiation without them.
@@ -197,15 +180,6 @@ __device__ inline uint32_t out_size(const BamOut &m, uint32_t i, uint32_t *err) 
   if constexpr (OPT)
     if (m.rg_on && !rg_seen && !tag_dropped(m.drop, KEY_RG)) size += 4 + m.rg_len;  // ... else appended behind the last field
   return size;
-}
-// Output record k of a MERGED stream (elp_emit_merged_bam) comes from one of two contexts: src[k] = rank of the record in the first
-// context's sorted output, or MERGE_SECOND | its rank in the second's.  src == nullptr: one context, output record k = perm[k].
-__device__ __forceinline__ const BamOut &out_source(const BamOut &m, const BamOut &m2, const uint32_t *__restrict__ src, uint64_t k, uint32_t *i) {
-  if (!src) { *i = m.perm[k]; return m; }
-  const uint32_t s = src[k];
-  const BamOut &mm = (s & MERGE_SECOND) ? m2 : m;
-  *i = mm.perm[s & ~MERGE_SECOND];
-  return mm;
 }
 template <bool OPT>
 __global__ __launch_bounds__(256) void k_bam_out_sizes(BamOut m, BamOut m2, const uint32_t *__restrict__ src, uint64_t k0, uint32_t cnt, uint32_t *__restrict__ sizes,
@@ -573,15 +547,29 @@ int elp_stage_bam(elp_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint
 }
 
 // the chunked size / scan / gather loop of both emit calls; src (device, n_out entries) or nullptr
-// bgzf: the stream leaves as BGZF blocks (stored DEFLATE, bgzf.hip), framed on the device pass by pass
+// fmt: the format of the stream - BAM records as they are; BGZF: the same as BGZF blocks (bgzf.hip), framed on the device pass by pass;
+// SAM: lines (sam.hip's kernels, with the names `nm`, which the other formats do not read).  who: the entry point, for error messages
+enum class OutFormat { BAM, BGZF, SAM };
 static int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint32_t *src, uint64_t n_out, uint64_t max_raw_rec, uint8_t *out, uint64_t cap,
-                       uint64_t *n_bytes_out, bool bgzf = false) {
+                       uint64_t *n_bytes_out, OutFormat fmt, const SamNames &nm, const char *who) {
+  const bool bgzf = fmt == OutFormat::BGZF, sam = fmt == OutFormat::SAM;
   // records per device pass: sizes and offsets of a pass are scanned in 32 bits, so a pass must stay below 4 GiB of output.  An output
   // record is never longer than the staged one (integer fields only shrink when re-encoded) - except that elp_clean_sam may have added
   // ONE CIGAR operation (4 bytes), and elp_set_replace_read_group may have made the record's RG field longer or added one (RG:Z:<id> =
   // 4 + id_len bytes; the caller adds that to max_raw_rec) - so the largest staged record + 4 (+ 4 + id_len) bounds it; BGZF framing adds
   // 26 bytes per 65280 (< 0.1 %: the bound leaves 1/64 of headroom).  A tag filter only takes bytes away.
-  uint32_t CHUNK = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1u << 21, 0xFC000000ull / (std::max<uint64_t>(max_raw_rec, 64) + 4)));
+  //   SAM text can be LONGER than the staged record, so its passes have a bound of their own:
+  // 5 x staged record + both reference names + 64.  Part by part, text against staged bytes (block_size field included):
+  //   fixed fields  FLAG 5, POS 11, MAPQ 3, PNEXT 11, TLEN 11, a "*" CIGAR 1, ten tabs and the newline 11 = 53 <= 64, beside 36 staged bytes
+  //   QNAME         l_name - 1 for l_name;  RNAME and RNEXT: the two names (or one byte each)
+  //   CIGAR         at most 9 digits + the operation = 10 for 4 (the one operation elp_clean_sam may add: 10, inside 5 x 36 - 64 = 116 spare)
+  //   SEQ + QUAL    2 l_seq for (l_seq + 1) / 2 + l_seq
+  //   a field       6 ("\tXX:T:") + value for 3 + value: A 7 for 4; c "-128" 10 for 4; s 12 for 5; i "-2147483648" 17 for 7; f 6 + 15 for 7;
+  //                 Z 6 + n for 4 + n; B 7 + elements for 8 + elements, an element with its comma: c "-128," 5 for 1 (the worst ratio
+  //                 of all), s 7 for 2, i 12 for 4, f 16 for 4
+  //   RG replaced   "\tRG:Z:<id>" = 6 + id_len: the caller's max_raw_rec holds 4 + id_len for it, five times that is more
+  const uint64_t rec_bound = sam ? 5 * max_raw_rec + 2 * (uint64_t)nm.max_name + 64 : std::max<uint64_t>(max_raw_rec, 64) + 4;
+  uint32_t CHUNK = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1u << 21, 0xFC000000ull / rec_bound));
   if (c->tune.emit_pass > 0) CHUNK = std::min<uint32_t>(CHUNK, (uint32_t)c->tune.emit_pass);  // (elp_set_tuning: tests)
   uint64_t total = 0;
   hipStream_t st = c->stream;
@@ -596,15 +584,17 @@ static int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint
     uint32_t *offs = sizes + cnt + 8, *err = offs + cnt + 8;
     ELP_HIP(c, hipMemsetAsync(err, 0, 4, st));
     const bool opt = m.drop != nullptr || m.rg_on;  // (m2 shares m's settings: elp_emit_merged_bam checks)
-    if (opt) ELP_LAUNCH(c, "emit_bam_sizes", k_bam_out_sizes<true>, dim3(blocks_for(cnt, 256)), dim3(256), 0, m, m2, src, k0, cnt, sizes, err);
+    if (sam) ELP_TRY(sam_sizes_launch(c, m, m2, nm, src, k0, cnt, sizes, err));
+    else if (opt) ELP_LAUNCH(c, "emit_bam_sizes", k_bam_out_sizes<true>, dim3(blocks_for(cnt, 256)), dim3(256), 0, m, m2, src, k0, cnt, sizes, err);
     else ELP_LAUNCH(c, "emit_bam_sizes", k_bam_out_sizes<false>, dim3(blocks_for(cnt, 256)), dim3(256), 0, m, m2, src, k0, cnt, sizes, err);
     uint32_t chunk_bytes = 0;
     ELP_TRY(exclusive_scan_u32(c, sizes, offs, cnt, &chunk_bytes));
     uint32_t he = 0;
     ELP_HIP(c, hipMemcpyAsync(&he, err, 4, hipMemcpyDeviceToHost, st));
     ELP_HIP(c, elp::stream_wait(st));
-    if (he & 16u) return set_error(c, ELP_ERR_UNSUPPORTED, "elp_emit_sorted_bam: H-typed optional field");
-    if (he) return set_error(c, ELP_ERR_DATA, "elp_emit_sorted_bam: malformed optional fields");
+    if (he & 16u) return set_error(c, ELP_ERR_UNSUPPORTED, "%s: H-typed optional field", who);
+    if (he & 32u) return set_error(c, ELP_ERR_DATA, "%s: a record's refid or next_refid is outside the dictionary", who);
+    if (he) return set_error(c, ELP_ERR_DATA, "%s: malformed optional fields", who);
     // (BGZF: the size of the stored form - what the pass needs room for; the compressed members are never larger, their actual size is
     // known behind the device pass.  A size query returns this upper bound: framed pass by pass it is never below the stored form of the
     // members the carried bytes make)
@@ -612,12 +602,13 @@ static int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint
     const uint64_t held = (uint64_t)carry.size(), pass_bytes = held + chunk_bytes;  // (held < 65280: the pass stays below 4 GiB, CHUNK's headroom)
     const uint64_t frame_bytes = !bgzf || k0 + cnt >= n_out ? pass_bytes : pass_bytes / BGZF_MEMBER_BYTES * BGZF_MEMBER_BYTES;
     uint64_t out_bytes = bgzf ? (frame_bytes ? bgzf_framed_size(frame_bytes) : 0) : (uint64_t)chunk_bytes;
-    if (total + out_bytes > cap) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bam: output buffer too small (%llu bytes needed so far)", (unsigned long long)(total + out_bytes));
+    if (total + out_bytes > cap) return set_error(c, ELP_ERR_ARG, "%s: output buffer too small (%llu bytes needed so far)", who, (unsigned long long)(total + out_bytes));
     uint8_t *d_out;
     ELP_TRY(scratch(c, 5, (size_t)pass_bytes + 64, &d_out));
     if (held) ELP_HIP(c, hipMemcpyAsync(d_out, carry.data(), held, hipMemcpyHostToDevice, st));
     const unsigned grid = std::min<unsigned>(blocks_for((uint64_t)cnt * 64, 256), (unsigned)c->n_cu * 32);
-    if (opt) ELP_LAUNCH(c, "emit_bam", k_bam_out_emit<true>, dim3(grid), dim3(256), 0, m, m2, src, k0, cnt, (const uint32_t *)offs, d_out + held);
+    if (sam) ELP_TRY(sam_emit_launch(c, m, m2, nm, src, k0, cnt, offs, d_out));
+    else if (opt) ELP_LAUNCH(c, "emit_bam", k_bam_out_emit<true>, dim3(grid), dim3(256), 0, m, m2, src, k0, cnt, (const uint32_t *)offs, d_out + held);
     else ELP_LAUNCH(c, "emit_bam", k_bam_out_emit<false>, dim3(grid), dim3(256), 0, m, m2, src, k0, cnt, (const uint32_t *)offs, d_out + held);
     const uint8_t *d_send = d_out;
     if (bgzf) {
@@ -654,7 +645,7 @@ int elp_emit_sorted_bam(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_byte
   ELP_TRY(radix_check(c));
   if (c->raw_n != c->n) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bam: records were not staged with elp_stage_bam");
   const BamOut m = bam_out_of(c);
-  return emit_stream(c, m, m, nullptr, c->n - c->n_sr, c->max_raw_rec + out_growth(c), out, cap, n_bytes_out);
+  return emit_stream(c, m, m, nullptr, c->n - c->n_sr, c->max_raw_rec + out_growth(c), out, cap, n_bytes_out, OutFormat::BAM, SamNames{}, "elp_emit_sorted_bam");
 }
 
 // The same records as BGZF blocks (utils/bgzf/bgzf-files.go:324-383): members of at most 65280 input bytes, COMPRESSED on the device
@@ -669,7 +660,7 @@ int elp_emit_sorted_bgzf(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_byt
   ELP_TRY(radix_check(c));
   if (c->raw_n != c->n) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_bgzf: records were not staged with elp_stage_bam");
   const BamOut m = bam_out_of(c);
-  return emit_stream(c, m, m, nullptr, c->n - c->n_sr, c->max_raw_rec + out_growth(c), out, cap, n_bytes_out, true);
+  return emit_stream(c, m, m, nullptr, c->n - c->n_sr, c->max_raw_rec + out_growth(c), out, cap, n_bytes_out, OutFormat::BGZF, SamNames{}, "elp_emit_sorted_bgzf");
 }
 
 // MergeSortedFilesSplitPerChromosome (sam/split-merge.go:410-576) with payloads: the records of `groups` and of `spread` as ONE stream in
@@ -697,17 +688,29 @@ static int two_context_checks(elp_ctx *groups, elp_ctx *spread, const char *who)
     return set_error(groups, ELP_ERR_ARG, "%s: one context has replaced its reference dictionary, the other has not (elp_replace_reference_dictionary)", who);
   return 0;
 }
-static int emit_two(elp_ctx *groups, elp_ctx *spread, const uint32_t *src, uint64_t n_out, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out, bool bgzf) {
+static SamNames sam_names_of(const elp_ctx *c) { return SamNames{c->ref_names.p, c->ref_names_off.p, c->n_ref, c->max_ref_name}; }
+// what the SAM emitters ask beyond their BAM counterparts: the names of the dictionary in force, in a stream of two contexts equal ones
+static int sam_names_checks(elp_ctx *c, elp_ctx *other, const char *who) {
+  if (!c->have_ref_names || (other && !other->have_ref_names))
+    return set_error(c, ELP_ERR_ARG, "%s: the reference names are not set (elp_set_reference_names_flat, for the dictionary the context holds now)", who);
+  if (other && (c->h_ref_names != other->h_ref_names || c->h_ref_names_off != other->h_ref_names_off))
+    return set_error(c, ELP_ERR_ARG, "%s: the two contexts' reference names differ (elp_set_reference_names_flat)", who);
+  return 0;
+}
+static int emit_two(elp_ctx *groups, elp_ctx *spread, const uint32_t *src, uint64_t n_out, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out, OutFormat fmt,
+                    const char *who) {
   const BamOut mg = bam_out_of(groups);
   BamOut ms = bam_out_of(spread);
   ms.drop = mg.drop; ms.rg_new = mg.rg_new;  // (equal contents, checked by two_context_checks; both on this device)
-  return emit_stream(groups, mg, ms, src, n_out, std::max(groups->max_raw_rec, spread->max_raw_rec) + out_growth(groups), out, cap, n_bytes_out, bgzf);
+  const SamNames nm = fmt == OutFormat::SAM ? sam_names_of(groups) : SamNames{};  // (equal in both contexts: sam_names_checks)
+  return emit_stream(groups, mg, ms, src, n_out, std::max(groups->max_raw_rec, spread->max_raw_rec) + out_growth(groups), out, cap, n_bytes_out, fmt, nm, who);
 }
 
-static int emit_merged(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out, bool bgzf, const char *who) {
+static int emit_merged(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out, OutFormat fmt, const char *who) {
   if (!groups || !spread || groups == spread || !n_bytes_out) return ELP_ERR_ARG;
   if (groups->derived.sorted_qname || spread->derived.sorted_qname) return merge_refuses_queryname(groups, who);
   ELP_TRY(two_context_checks(groups, spread, who));
+  if (fmt == OutFormat::SAM) ELP_TRY(sam_names_checks(groups, spread, who));
   uint64_t *slots = nullptr;
   ELP_TRY(merge_spread_slots(groups, spread, &slots));  // checks: both coordinate-sorted or keep-ordered (then: monotonic), one device
   const uint64_t ng = groups->n - groups->n_sr, ns = spread->n - spread->n_sr, n_out = ng + ns;
@@ -721,18 +724,19 @@ static int emit_merged(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t 
   if (ns) ELP_LAUNCH(groups, "merge_mark", k_merge_mark, dim3(blocks_for(ns, 256)), dim3(256), 0, ns, (const uint64_t *)slots, is_spread, src);
   ELP_TRY(exclusive_scan_u32(groups, is_spread, before, n_out, nullptr));
   ELP_LAUNCH(groups, "merge_fill", k_merge_fill, dim3(blocks_for(n_out, 256)), dim3(256), 0, n_out, (const uint32_t *)is_spread, (const uint32_t *)before, src);
-  return emit_two(groups, spread, src, n_out, out, cap, n_bytes_out, bgzf);
+  return emit_two(groups, spread, src, n_out, out, cap, n_bytes_out, fmt, who);
 }
 
 // MergeUnsortedFilesSplitPerChromosome (sam/split-merge.go:581-619) with payloads: the unmapped file (split id 0 of `groups`), the spread
 // file, then the group files in index order, each in its own (input) order
-static int emit_concat(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out, bool bgzf, const char *who) {
+static int emit_concat(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out, OutFormat fmt, const char *who) {
   if (!groups || !spread || groups == spread || !n_bytes_out) return ELP_ERR_ARG;
   if (!groups->derived.sorted_keep || !groups->derived.sorted_keep_by_split)
     return set_error(groups, ELP_ERR_ARG, "%s: the groups context must hold a keep permutation ordered by split id (elp_order_keep with by_split = 1)", who);
   if (!spread->derived.sorted_keep || spread->derived.sorted_keep_by_split)
     return set_error(groups, ELP_ERR_ARG, "%s: the spread context must hold a plain keep permutation (elp_order_keep with by_split = 0)", who);
   ELP_TRY(two_context_checks(groups, spread, who));
+  if (fmt == OutFormat::SAM) ELP_TRY(sam_names_checks(groups, spread, who));
   if (groups->device != spread->device) return set_error(groups, ELP_ERR_ARG, "%s: contexts on different devices", who);
   ELP_HIP(groups, hipSetDevice(groups->device));
   const uint64_t ng = groups->n - groups->n_sr, ns = spread->n - spread->n_sr, n_out = ng + ns;
@@ -742,21 +746,42 @@ static int emit_concat(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t 
   ELP_TRY(scratch(groups, 6, n_out + 16, &w));
   ELP_HIP(groups, elp::stream_wait(spread->stream));  // (the spread's permutation is complete)
   ELP_TRY(keep_concat_src(groups, ng, ns, w + n_out + 8, w));
-  return emit_two(groups, spread, w, n_out, out, cap, n_bytes_out, bgzf);
+  return emit_two(groups, spread, w, n_out, out, cap, n_bytes_out, fmt, who);
 }
 
 int elp_emit_merged_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
-  return emit_merged(groups, spread, out, cap, n_bytes_out, false, "elp_emit_merged_bam");
+  return emit_merged(groups, spread, out, cap, n_bytes_out, OutFormat::BAM, "elp_emit_merged_bam");
 }
 // The merged stream as BGZF members, as elp_emit_sorted_bgzf frames the sorted one: `sfm`'s final output leaves the device compressed
 int elp_emit_merged_bgzf(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
-  return emit_merged(groups, spread, out, cap, n_bytes_out, true, "elp_emit_merged_bgzf");
+  return emit_merged(groups, spread, out, cap, n_bytes_out, OutFormat::BGZF, "elp_emit_merged_bgzf");
 }
 int elp_emit_concat_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
-  return emit_concat(groups, spread, out, cap, n_bytes_out, false, "elp_emit_concat_bam");
+  return emit_concat(groups, spread, out, cap, n_bytes_out, OutFormat::BAM, "elp_emit_concat_bam");
 }
 int elp_emit_concat_bgzf(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
-  return emit_concat(groups, spread, out, cap, n_bytes_out, true, "elp_emit_concat_bgzf");
+  return emit_concat(groups, spread, out, cap, n_bytes_out, OutFormat::BGZF, "elp_emit_concat_bgzf");
+}
+
+// The same streams as SAM text (sam.hip): FormatAlignment (sam/sam-files.go:563-598) of the records the BAM calls above write, in their
+// order, under their checks; no header lines, no framing - a size query (out = NULL) is exact.  The names of the dictionary in force must
+// be set (elp_set_reference_names_flat).
+int elp_emit_sorted_sam(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
+  if (!c || !n_bytes_out) return ELP_ERR_ARG;
+  ELP_HIP(c, hipSetDevice(c->device));
+  if (!c->derived.sorted) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_sam: call elp_sort_coordinate, elp_sort_queryname or elp_order_keep first");
+  ELP_TRY(radix_check(c));
+  if (c->raw_n != c->n) return set_error(c, ELP_ERR_ARG, "elp_emit_sorted_sam: records were not staged with elp_stage_bam");
+  ELP_TRY(sam_names_checks(c, nullptr, "elp_emit_sorted_sam"));
+  const BamOut m = bam_out_of(c);
+  const SamNames nm = sam_names_of(c);
+  return emit_stream(c, m, m, nullptr, c->n - c->n_sr, c->max_raw_rec + out_growth(c), out, cap, n_bytes_out, OutFormat::SAM, nm, "elp_emit_sorted_sam");
+}
+int elp_emit_merged_sam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
+  return emit_merged(groups, spread, out, cap, n_bytes_out, OutFormat::SAM, "elp_emit_merged_sam");
+}
+int elp_emit_concat_sam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out) {
+  return emit_concat(groups, spread, out, cap, n_bytes_out, OutFormat::SAM, "elp_emit_concat_sam");
 }
 
 }  // extern "C"

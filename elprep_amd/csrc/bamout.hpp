@@ -1,0 +1,53 @@
+// bamout.hpp — what the emitters of both output formats share: the columns and staged bytes an output record is gathered from (BamOut),
+// the tag filter's look-up and the choice of the source context in a stream made of two.  bam.hip writes BAM records from them
+// (formatBamAlignment), sam.hip SAM lines (FormatAlignment); emit_stream (bam.hip) is the loop around either pair of kernels.
+#pragma once
+
+#include "common.hpp"
+#include "bamtag.hpp"
+
+namespace elp {
+
+struct BamOut {
+  uint64_t n_out;
+  const uint32_t *perm;
+  const uint8_t *raw;
+  const uint64_t *raw_off;   // per staged record: offset of its BAM record in raw (n + 1)
+  const int32_t *refid, *pos, *next_refid, *pnext, *tlen;
+  const uint16_t *flag;
+  const uint8_t *mapq;
+  const uint32_t *l_seq;
+  const uint64_t *qname_off, *cigar_off, *qual_off;
+  const uint8_t *qname, *qual;
+  const uint32_t *cigar;
+  const uint32_t *drop;      // elp_set_tag_filter: bit k = fields with the 16-bit key k stay behind (65536 bits); nullptr = no filter
+  const uint8_t *rg_new;     // elp_set_replace_read_group: the id every record goes out with (rg_on), rg_len bytes
+  uint32_t rg_len, rg_on;
+};
+constexpr uint32_t KEY_RG = tag_key_of('R', 'G');
+// filters2's RemoveOptionalFields / KeepOptionalFields (filters/simple-filters.go:235-288) as one look-up: every field of a key goes or stays
+__device__ __forceinline__ bool tag_dropped(const uint32_t *__restrict__ drop, uint32_t key) { return drop && ((drop[key >> 5] >> (key & 31)) & 1u); }
+// Output record k of a MERGED stream (elp_emit_merged_bam) comes from one of two contexts: src[k] = rank of the record in the first
+// context's sorted output, or MERGE_SECOND | its rank in the second's.  src == nullptr: one context, output record k = perm[k].
+__device__ __forceinline__ const BamOut &out_source(const BamOut &m, const BamOut &m2, const uint32_t *__restrict__ src, uint64_t k, uint32_t *i) {
+  if (!src) { *i = m.perm[k]; return m; }
+  const uint32_t s = src[k];
+  const BamOut &mm = (s & MERGE_SECOND) ? m2 : m;
+  *i = mm.perm[s & ~MERGE_SECOND];
+  return mm;
+}
+
+// SAM text (sam.hip): the @SQ SN strings of the stream's dictionary (elp_set_reference_names_flat), name of refid r = names[name_off[r] ..
+// name_off[r + 1]).  A stream of two contexts has ONE table: both hold equal names (checked, as for the tag filter).
+struct SamNames {
+  const uint8_t *names;
+  const uint32_t *name_off;
+  int32_t n_ref;
+  uint32_t max_name;  // bytes of the longest name (the host's bound of a pass, emit_stream)
+};
+// the two passes of a SAM chunk, queued on c->stream under the profile names emit_sam_sizes and emit_sam (sizes, err, offs, out as the
+// BAM kernels take them)
+int sam_sizes_launch(elp_ctx *c, const BamOut &m, const BamOut &m2, const SamNames &nm, const uint32_t *src, uint64_t k0, uint32_t cnt, uint32_t *sizes, uint32_t *err);
+int sam_emit_launch(elp_ctx *c, const BamOut &m, const BamOut &m2, const SamNames &nm, const uint32_t *src, uint64_t k0, uint32_t cnt, const uint32_t *offs, uint8_t *out);
+
+}  // namespace elp

@@ -186,6 +186,14 @@ struct elp_ctx {
   elp::DVec<uint8_t> rg_ids;    // header read-group ids, concatenated (RG:Z -> rgid)
   elp::DVec<uint32_t> rg_ids_off;
   bool have_rg_ids = false;
+  // elp_set_reference_names_flat (sam.hip): the @SQ SN strings of the dictionary in force, for the SAM emitters; dropped wherever the
+  // reference table is replaced (elp_set_header, install_dictionary)
+  elp::DVec<uint8_t> ref_names;
+  elp::DVec<uint32_t> ref_names_off;       // n_ref + 1
+  std::string h_ref_names;                 // the host's copies (the two-context emitters compare them)
+  std::vector<uint32_t> h_ref_names_off;
+  uint32_t max_ref_name = 0;
+  bool have_ref_names = false;
   // optional-field settings of a run (bam.hip: elp_set_tag_filter, elp_set_replace_read_group); elp_reset and elp_set_header clear both
   static constexpr size_t TAG_WORDS = 65536 / 32;
   bool tag_filter = false;             // tag_drop holds a table: bit k of it = fields with the 16-bit key k do not go out

@@ -256,6 +256,7 @@ int install_dictionary(elp_ctx *c, int32_t n_ref, const int32_t *ref_len) {
   const std::vector<int32_t> len(ref_len, ref_len + n_ref);  // (ref_len may be the context's own copy)
   c->n_ref = n_ref;
   c->h_ref_len = len;
+  c->have_ref_names = false;  // (the names belong to the dictionary that leaves)
   if (n_ref) ELP_HIP(c, hipMemcpyAsync(c->ref_len.p, c->h_ref_len.data(), (size_t)n_ref * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   ELP_HIP(c, elp::stream_wait(c->stream));
   c->h_ref_seq.assign((size_t)n_ref, nullptr);
@@ -361,6 +362,7 @@ int elp_set_header(elp_ctx *c, const elp_header *h) {
   c->n_ref0 = h->n_ref;          // (the dictionary elp_reset returns to behind elp_replace_reference_dictionary)
   c->h_ref_len0 = c->h_ref_len;
   c->dict_replaced = false;
+  c->have_ref_names = false;     // (the SAM emitters' names belong to the dictionary: the host sets the new header's)
   c->h_rg_lib.assign(h->rg_lib, h->rg_lib + h->n_rg);
   c->h_rg_cov.assign(h->rg_cov, h->rg_cov + h->n_rg);
   for (int i = 0; i < h->n_rg; i++) {

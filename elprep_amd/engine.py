@@ -145,6 +145,8 @@ class Engine:
 
     def reset(self):
         self._check(self.L.elp_reset(self.h))
+        if getattr(self, "_n_ref_now", None) is not None:
+            self._names_set = False  # (the replaced dictionary's names left with it: the SAM emitters set the header's again)
         self._n_ref_now = None  # (elp_reset returns to the header's dictionary)
 
     def snapshot(self):
@@ -222,6 +224,52 @@ class Engine:
     def emit_concat_bgzf(self, spread: "Engine") -> np.ndarray:
         """emit_concat_bam's stream as BGZF members (elp_emit_concat_bgzf)"""
         return self._emit_two(self.L.elp_emit_concat_bgzf, spread)
+
+    # ---- SAM text out (include/elprep_hip.h: FormatAlignment on the device)
+    def _n_ref_in_force(self) -> int:
+        n_ref = getattr(self, "_n_ref_now", None)  # (set by replace_reference_dictionary, until reset())
+        return self.header.n_ref if n_ref is None else n_ref
+
+    def set_reference_names(self, names: Optional[Sequence] = None):
+        """the @SQ SN strings (str or bytes) of the dictionary the context holds NOW, for the SAM emitters (elp_set_reference_names_flat);
+        default: the header's ref_names.  Set them again behind replace_reference_dictionary (the new dictionary's names).  The C call is
+        told no count - it reads as many names as the dictionary in force has contigs -, so a list of another length is refused here"""
+        if names is None and getattr(self, "_n_ref_now", None) is not None:
+            raise ElpError(-1, "set_reference_names: the dictionary was replaced, the header's names are the old contigs': pass the new names")
+        names = self.header.ref_names if names is None else names
+        if len(names) != self._n_ref_in_force():
+            raise ElpError(-1, "set_reference_names: %d names, the context's dictionary has %d contigs" % (len(names), self._n_ref_in_force()))
+        cat, off, _ = _flat_names(names)
+        self._check(self.L.elp_set_reference_names_flat(self.h, _vp(cat), _vp(off)))
+        self._names_set = True
+
+    def _header_names(self):
+        # the names come from Header.ref_names the first time a SAM emitter runs - but never under a replaced dictionary: the header's
+        # names are the OLD contigs', the caller sets the new ones (until then the C call returns ELP_ERR_ARG)
+        if not getattr(self, "_names_set", False) and getattr(self, "_n_ref_now", None) is None:
+            self.set_reference_names()
+
+    def emit_sorted_sam(self, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """emit_sorted_bam's records as SAM lines, without header text (elp_emit_sorted_sam); the size query is exact"""
+        self._header_names()
+        n = C.c_uint64()
+        if out is None:
+            self._check(self.L.elp_emit_sorted_sam(self.h, C.c_void_p(0), 0, C.byref(n)))
+            out = np.empty(int(n.value), dtype=np.uint8)
+        self._check(self.L.elp_emit_sorted_sam(self.h, _vp(out), out.size, C.byref(n)))
+        return out[:int(n.value)]
+
+    def emit_merged_sam(self, spread: "Engine") -> np.ndarray:
+        """emit_merged_bam's stream as SAM lines (elp_emit_merged_sam)"""
+        self._header_names()
+        spread._header_names()
+        return self._emit_two(self.L.elp_emit_merged_sam, spread)
+
+    def emit_concat_sam(self, spread: "Engine") -> np.ndarray:
+        """emit_concat_bam's stream as SAM lines (elp_emit_concat_sam)"""
+        self._header_names()
+        spread._header_names()
+        return self._emit_two(self.L.elp_emit_concat_sam, spread)
 
     # ---- fused predicates, split / merge bookkeeping (include/elprep_hip.h)
     def filter_records(self, remove_unmapped=False, remove_unmapped_strict=False, min_mapq=0, remove_non_exact=False, remove_duplicates=False,
@@ -305,13 +353,13 @@ class Engine:
         References and known sites are set AFTER the call, under the new refids."""
         m = np.ascontiguousarray(new_of_old, dtype=np.int32).reshape(-1)
         ln = np.ascontiguousarray(ref_len_new, dtype=np.int32).reshape(-1)
-        n_ref = getattr(self, "_n_ref_now", None)
-        n_ref = self.header.n_ref if n_ref is None else n_ref
+        n_ref = self._n_ref_in_force()
         if m.size != n_ref:  # (the library reads new_of_old[0 .. n_ref) of the dictionary in force)
             raise ElpError(-1, "replace_reference_dictionary: new_of_old has %d entries, the context's dictionary %d contigs" % (m.size, n_ref))
         n = C.c_uint64()
         self._check(self.L.elp_replace_reference_dictionary(self.h, _vp(m), int(ln.size), _vp(ln), C.byref(n)))
         self._n_ref_now = int(ln.size)  # until reset() / a new header
+        self._names_set = False         # (the C side dropped the old dictionary's names)
         return int(n.value)
 
     def copy_records_from(self, src: "Engine", idx: np.ndarray, new_split: Optional[int] = None, tag_sr=False):

@@ -278,7 +278,7 @@ def _order_call(e, order: str):
 
 
 def emit_merged_device(groups, spread, part, group_of_ref: np.ndarray, n_groups: int, owner: np.ndarray, rank: int, world: int,
-                       order: str = "coordinate") -> np.ndarray:
+                       order: str = "coordinate", fmt: str = "bam") -> np.ndarray:
     """The merge phase across ranks through the C ABI (MergeSortedFilesSplitPerChromosome, sam/split-merge.go:410-576): the spread split's
     owner sends every rank the spread reads of that rank's contig groups - in the spread file's coordinate order, with the FLAG and QUAL
     columns as the path left them (elp_exchange_records; elp_copy_records for its own) - into the rank's `part` context; every rank then
@@ -287,7 +287,10 @@ def emit_merged_device(groups, spread, part, group_of_ref: np.ndarray, n_groups:
     their group boundaries in @SQ order + the unmapped split.  `groups` and `spread` are coordinate-sorted and hold the inflated BAM
     records (elp_stage_bam); `spread` is empty on every rank but the owner; `part` is an empty context of the same device group.
     order = "keep": `groups` and `spread` hold sorted input in input order (order_keep); `part`, which receives its reads in the spread
-    file's order, is ordered the same way."""
+    file's order, is ordered the same way.
+    fmt = "sam": the stream as SAM lines without header text (elp_emit_merged_sam; the names are the header's ref_names)."""
+    if fmt not in ("bam", "sam"):
+        raise ValueError("fmt must be 'bam' or 'sam', not %r" % (fmt,))
     spread_owner = int(owner[n_groups + 1])
     part.reset()
     if rank == spread_owner and spread.n:
@@ -308,7 +311,7 @@ def emit_merged_device(groups, spread, part, group_of_ref: np.ndarray, n_groups:
             if send_to >= 0 or recv_from >= 0:
                 (spread if rank == spread_owner else part).exchange_records(send_to, idx, part if recv_from >= 0 else None, recv_from, new_split=0)
     _order_call(part, order)(False)
-    return groups.emit_merged_bam(part)
+    return groups.emit_merged_sam(part) if fmt == "sam" else groups.emit_merged_bam(part)
 
 
 # ------------------------------------------------------------------------------------------------ output order
@@ -576,11 +579,11 @@ class SfmRank:
         for e in self.engines:
             e.apply_bqsr(lut, present, max_cycle, fetch=False)
 
-    def emit_merged(self, group_of_ref: np.ndarray, n_groups: int, owner: np.ndarray, order: str = "coordinate") -> np.ndarray:
+    def emit_merged(self, group_of_ref: np.ndarray, n_groups: int, owner: np.ndarray, order: str = "coordinate", fmt: str = "bam") -> np.ndarray:
         """the merge phase of this rank (emit_merged_device): the BAM records of its contig groups' output with the spread reads of those
         groups inserted - every context of the rank that sends or receives joins the device group first (the communicator the tables were
         reduced on, or the send-receive callback).  The records must have been staged from BAM bytes (route(..., stage=...)).  order: what
-        step() was given."""
+        step() was given.  fmt: "bam" (records) or "sam" (lines, without header text)."""
         from .engine import Engine
         if getattr(self, "_part", None) is None:
             self._part = Engine(self.header, self._device_ordinal)
@@ -593,7 +596,7 @@ class SfmRank:
                     else:
                         e.group_init_transport(self.comm.rank, self.comm.world, lambda v: None)
                         e.group_set_p2p(self.comm.sendrecv)
-        return emit_merged_device(self.engines[0], self.engines[1], self._part, group_of_ref, n_groups, owner, self.comm.rank, self.comm.world, order)
+        return emit_merged_device(self.engines[0], self.engines[1], self._part, group_of_ref, n_groups, owner, self.comm.rank, self.comm.world, order, fmt)
 
     def close(self):
         if self._side is not None:

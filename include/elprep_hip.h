@@ -184,6 +184,37 @@ int elp_emit_merged_bgzf(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_
 int elp_emit_concat_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out);
 int elp_emit_concat_bgzf(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out);
 
+/* ---- SAM text out (sam/sam-files.go:485-598; csrc/sam.hip) ----
+ * The writer of the reference picks the format by the file's extension (sam/aln-files.go:134-135): these are the ".sam" forms of the
+ * emitters above.  Each writes FormatAlignment(parseBamAlignment(record)) (:563-598, sam/bam-files.go:317-400) of every record its BAM
+ * counterpart writes, in the same order, from the same permutation: eleven fields separated by tabs, every optional field behind a tab,
+ * '\n'.  FLAG and MAPQ unsigned, POS / PNEXT (1-based) and TLEN signed decimal; RNAME = the name of refid, "*" below 0; RNEXT "*" for
+ * next_refid < 0, "=" for next_refid == refid, else the name; CIGAR from the CIGAR column (behind elp_clean_sam), "*" for no operation;
+ * SEQ one character per base of "=ACMGRSVTWYHKDBN" and EMPTY for l_seq 0 (the reference's loop writes nothing, not "*"); QUAL every byte
+ * of the QUAL column as it is now + 33 modulo 256 (BAM's 0xFF "missing" bytes leave as spaces, as the reference writes them).  Optional
+ * fields (formatSamTag :485-546) behind the tag filter and the read-group replacement, in the order the BAM emitters keep: A as :A:, c C
+ * s S i I as :i: + decimal (the parser makes int64 of all), Z as :Z:, B as :B:<subtype> and ",<value>" per element, f and B:f values as
+ * strconv.AppendFloat(float64(v), 'g', -1, 32) - the shortest decimal that reads back as the float32, exponent form "d.ddde+XX" for a
+ * decimal exponent below -4 or from 6 up, NaN, +Inf, -Inf (csrc/samtext.hpp) -, a replaced or added read group as "\tRG:Z:<id>".
+ * H fields: ELP_ERR_UNSUPPORTED, malformed fields: ELP_ERR_DATA, as in the BAM emitters.
+ *   No header text goes out: the host writes @HD, @SQ, @RG and @PG and then these bytes.  out = NULL is a size query and returns the
+ * EXACT size (text has no framing).  Checks, errors and concurrency rules are the BAM counterparts' (a permutation, records staged with
+ * elp_stage_bam, the two-context rules of elp_emit_merged_bam / elp_emit_concat_bam), and: the reference names must be set
+ * (ELP_ERR_ARG), in a stream of two contexts equal names in both (ELP_ERR_ARG - the rule of the tag filters); a staged next_refid that
+ * the dictionary does not hold is ELP_ERR_DATA.  elp_set_tuning("emit_pass") caps these passes too.
+ * Reads: what the BAM counterpart reads, and the names.  Writes: `out` only; the calls invalidate nothing.
+ * elp_set_reference_names_flat: the @SQ SN strings of the context's CURRENT dictionary, behind each other: name_off[r] .. name_off[r + 1]
+ *   = name of refid r (n_ref + 1 offsets).  Call after elp_set_header, for the dictionary the context holds now.  The names belong to
+ *   that dictionary and are dropped wherever the reference table is replaced: elp_set_header, elp_replace_reference_dictionary (the host
+ *   then sets the NEW names), an elp_reset that undoes a replacement; a plain elp_reset keeps them (the next file of the same header).
+ *   ELP_ERR_ARG: no header, NULL arrays with n_ref > 0, offsets that decrease, an empty name, a name "*" or "=", two equal names -
+ *   names are distinct, so the device decides "=" by comparing refids where the reference compares strings (bam-files.go:344-346).
+ *   Writes: the names and an offsets table in HBM. */
+int elp_set_reference_names_flat(elp_ctx *ctx, const uint8_t *names, const uint32_t *name_off);
+int elp_emit_sorted_sam(elp_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out);
+int elp_emit_merged_sam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out);
+int elp_emit_concat_sam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out);
+
 /* ---- the options that touch a record's optional fields (filters/simple-filters.go; cmd/filter.go:696-902) ----
  * The settings of elp_set_tag_filter and elp_set_replace_read_group belong to a run: elp_reset and elp_set_header clear both.
  *
