@@ -17,6 +17,7 @@
 // All cross-workgroup words are touched with agent-scope atomics; stale plain reads cannot occur because table entries
 // only ever change EMPTY -> value and tournaments are re-checked through the CAS return value.
 #include "common.hpp"
+#include "markdup_plan.hpp"
 
 namespace elp {
 
@@ -274,7 +275,6 @@ __global__ __launch_bounds__(256) void k_mate_table(MdCols m, const uint4 *__res
 // `fixed` (the host saw that most candidates take the table path) the followers are marked like table pairs and entered afterwards.
 // A thread handles MP_R records (one per 256-record tile of its workgroup) and issues the loads of all of them level by level - codes,
 // keys and name hashes; then Bloom words, the neighbour's key and the scores - before any test that needs them.
-constexpr int MP_R = 1;
 __global__ __launch_bounds__(256) void k_mate_pairs(MdCols m, const uint4 *__restrict__ fkey, uint8_t *__restrict__ code,
                                                     const uint32_t *__restrict__ hash32, const uint32_t *__restrict__ hash_lo, const uint32_t *__restrict__ bloom,
                                                     uint32_t bloom_mask, const uint32_t *__restrict__ coarse /* null: nobody announced a key */,
@@ -412,7 +412,6 @@ __device__ __forceinline__ uint64_t pair_entry(const MdCols &m, const uint4 &lat
 }
 // the pairs that formed in the mate table (or in the big groups' arrival-order pairing): their owners carry MC_TABBED in the code
 // column (one byte per record to scan; in aligner order next to none of them is marked)
-constexpr int PL_TILES = 8;
 __global__ __launch_bounds__(256) void k_pair_list_table(MdCols m, const uint4 *__restrict__ fkey, const uint32_t *__restrict__ mate,
                                                          const uint8_t *__restrict__ code, uint64_t *__restrict__ pk, uint32_t *__restrict__ pv,
                                                          uint32_t *np) {
@@ -553,9 +552,6 @@ __device__ __forceinline__ void pair_lost(const MdCols &m, const uint32_t *__res
   flag_out[mt] = (uint16_t)(flag_out[mt] | F_DUPLICATE);
 }
 
-constexpr int PB_THREADS = 256;
-constexpr int PB_TARGET = 384;     // the list is partitioned until a bucket holds at most this many entries on average
-constexpr int PB_CAP = 1024;       // table slots in LDS
 constexpr int PB_ECAP = 1024;      // entries whose table slot is remembered in LDS between the phases (the others look theirs up again)
 
 // table slot of entry {h32, o}: find-or-insert.  Returns -1 if the table is full.
@@ -729,7 +725,7 @@ __device__ __forceinline__ uint16_t flag_in_of(uint16_t f, uint8_t state) { retu
 // (a thread takes eight consecutive records per round: one 16-byte load of their flags, one 8-byte load of their states.  A few persistent
 // workgroups, each appending with ONE global atomic per flush of its LDS list: with a workgroup per 4096 records, 12 K of them queued at
 // the one counter for ~12 ns each - 0.15 of the kernel's 0.18 ms)
-constexpr int FLI_CAP = 4096, FLI_CHUNK = 2048;
+constexpr int FLI_CAP = 4096;
 __global__ __launch_bounds__(256) void k_frag_list(FrontCols m, uint4 *__restrict__ fkey, uint32_t *__restrict__ flist, uint32_t *nf,
                                                    unsigned long long *__restrict__ fbest, uint32_t *__restrict__ fwinner) {
   __shared__ uint32_t lq[FLI_CAP];
@@ -787,7 +783,6 @@ __global__ __launch_bounds__(256) void k_frag_list(FrontCols m, uint4 *__restric
 // record one DPP move away, whatever the wave - no border threads, no second fetch of a record's cache lines.  u = 63 w + l in [0, 315)
 // numbers the workgroup's records; the tests' results and what a follower needs of its leader (key, score) go through LDS; records
 // u = 2 .. 313 are the workgroup's own.
-constexpr int MF_THREADS = 320, MF_RECS = 312;
 template <bool ADAPT>
 __global__ __launch_bounds__(MF_THREADS) void k_md_front(FrontCols m, const int32_t *__restrict__ score, int32_t *__restrict__ upos_out, uint64_t *__restrict__ key_out,
                                                          uint4 *fkey, uint8_t *__restrict__ code, uint32_t *__restrict__ hash32, uint32_t *__restrict__ hash_lo, uint32_t *bloom,
@@ -905,10 +900,180 @@ __global__ __launch_bounds__(MF_THREADS) void k_md_front(FrontCols m, const int3
   }
 }
 
-static uint64_t table_size_for(uint64_t n) {
-  uint64_t t = 1024;
-  while (t < 2 * n + 16) t <<= 1;
-  return t;
+// ---------------- host side: one function per phase.  Every size, grid of the record count and scratch offset comes from markdup_plan.hpp
+// (MdSizes, MdScratch, frag_table_size, mate_plan); a phase computes none.  What a call works on: the record columns and the carved scratch
+struct MdBufs {
+  MdCols m;
+  uint32_t *table, *rep, *flist, *winner, *bloom, *coarse, *hash32, *tab_list, *hash_lo;  // (slot 6, from bloom on: carved by md_front)
+  unsigned long long *best;
+  uint4 *fkey;
+  uint8_t *code;
+  uint64_t *pk;  // slot 7: carved by md_front, when the number of true fragments is back
+  uint32_t *pv, *ftable, *fbits;
+  uint32_t *nf_dev, *np_dev, *n_table_dev;  // the call's counters (md_ctr): [0] true fragments, [1] pair entries, [16 + 16 k] 64 counters of table records
+  uint32_t *rep_of;                         // pair_win's buffer: free until the pair phase fills it
+};
+constexpr size_t MD_CTRS = 16 + 64 * 16;
+
+static int md_carve(elp_ctx *c, const MdScratch &L, MdBufs *b) {
+  b->m = MdCols{c->n, c->refid.p, c->flag.p, c->rgid.p, c->rg_lib.p, c->split.p, c->upos.p, c->score.p, c->qname_off.p, c->qname.p};
+  ELP_TRY(scratch(c, 0, L.table, &b->table));
+  ELP_TRY(scratch(c, 2, L.best, &b->best));
+  ELP_TRY(scratch(c, 3, L.winner, &b->winner));
+  ELP_TRY(scratch(c, 5, L.fkey, &b->fkey));
+  ELP_TRY(ensure(c, c->md_ctr, MD_CTRS));
+  ELP_TRY(scratch(c, 1, L.words1, &b->rep));
+  b->flist = b->rep + L.flist;
+  b->nf_dev = c->md_ctr.p, b->np_dev = c->md_ctr.p + 1, b->n_table_dev = c->md_ctr.p + 16;
+  b->rep_of = c->pair_win.p;
+  return 0;
+}
+
+// ---- fragments, first part: keys of all records + the list of true fragments.  The list's length comes back through the mailbox while
+// the stream runs on (the score kernel, when the adapt stage is this call's)
+static int md_frag_list(elp_ctx *c, const MdSizes &S, const MdBufs &B, const FrontCols &fc) {
+  hipStream_t st = c->stream;
+  ELP_HIP(c, hipMemsetAsync(c->md_ctr.p, 0, MD_CTRS * sizeof(uint32_t), st));  // every counter of this call in one fill
+  ELP_TRY(mailbox(c));
+  ELP_LAUNCH(c, "md_frag_list", k_frag_list, dim3(S.frag_list_grid(c->n_cu)), dim3(256), 0, fc, B.fkey, B.flist, B.nf_dev, B.best, B.winner);
+  ELP_HIP(c, hipMemcpyAsync(c->mail, B.nf_dev, 4, hipMemcpyDeviceToHost, st));
+  ELP_HIP(c, hipEventRecord(c->mail_ev, st));
+  return 0;
+}
+
+// ---- front: the fragments' table first (it is final before any pair looks its key up), then the front pass: mate codes, key hashes and
+// Bloom announcements, the pairs' fragment look-ups and the entries of the neighbour pairs
+static int md_front(elp_ctx *c, const MdSizes &S, const MdScratch &L, MdBufs &B, const FrontCols &fc, bool fuse_adapt, uint32_t *nf_out) {
+  hipStream_t st = c->stream;
+  ELP_TRY(scratch(c, 6, L.words6, &B.bloom));
+  B.coarse = B.bloom + L.coarse, B.hash32 = B.bloom + L.hash32, B.tab_list = B.bloom + L.tab_list, B.hash_lo = B.bloom + L.hash_lo;
+  B.code = reinterpret_cast<uint8_t *>(B.bloom + L.code);
+  ELP_HIP(c, hipMemsetAsync(B.bloom, 0, S.bw * sizeof(uint32_t), st));
+  ELP_HIP(c, elp::event_wait(c->mail_ev));
+  const uint32_t nf = *nf_out = c->mail[0];
+  const uint64_t Tf = frag_table_size(nf, S.T);
+  const MdScratch::Pairs P = L.pairs(Tf);
+  ELP_TRY(scratch(c, 7, P.words64, &B.pk));
+  uint32_t *const w7 = reinterpret_cast<uint32_t *>(B.pk);
+  B.pv = w7 + P.pv, B.ftable = w7 + P.ftable, B.fbits = w7 + P.fbits;
+  if (nf) {
+    ELP_HIP(c, hipMemsetAsync(B.ftable, 0xFF, Tf * sizeof(uint32_t), st));
+    ELP_LAUNCH(c, "md_frag_insert", k_frag_insert, dim3(blocks_for(nf, 256)), dim3(256), 0, B.m, (const uint4 *)B.fkey, (const uint32_t *)B.flist, nf, B.ftable, Tf - 1, B.rep, B.best);
+    ELP_LAUNCH(c, "md_frag_bits", k_frag_bits, dim3(blocks_for(Tf / 32, 256)), dim3(256), 0, (const uint32_t *)B.ftable, Tf / 32, B.fbits);
+  }
+  // the front pass also does the adapt stage's fixed-field part when that has not run yet
+  const auto front = fuse_adapt ? k_md_front<true> : k_md_front<false>;
+  ELP_LAUNCH(c, "md_front", front, dim3(S.front_grid), dim3(MF_THREADS), 0, fc, (const int32_t *)c->score.p, c->upos.p, c->key.p, B.fkey, B.code, B.hash32, B.hash_lo, B.bloom,
+             (uint32_t)(S.bw - 1), B.n_table_dev, (const uint32_t *)B.ftable, (const uint32_t *)B.fbits, nf ? Tf - 1 : (uint64_t)0, B.best, c->mate.p, c->pair_win.p, B.pk, B.pv, B.np_dev, S.nfx,
+             c->tune.mate_path == 0 ? 1 : 0);
+  return 0;
+}
+
+// ---- fragments, second part: the tournament among the fragments of pair-free groups (the pair bits are complete), queued in front of
+// the call's one unconditional wait: the number of records that need the mate table and, if pending, the adapt stage's quality-error word
+static int md_fragments(elp_ctx *c, const MdBufs &B, uint32_t nf, uint32_t *n_tab_out) {
+  hipStream_t st = c->stream;
+  if (nf) {
+    const unsigned fgrid = blocks_for(nf, 256);
+    ELP_LAUNCH(c, "md_frag_tie", k_frag_tie, dim3(fgrid), dim3(256), 0, B.m, (const uint32_t *)B.flist, nf, (const uint32_t *)B.rep, (const unsigned long long *)B.best, B.winner);
+    ELP_LAUNCH(c, "md_frag_flag", k_frag_flag, dim3(fgrid), dim3(256), 0, B.m, (const uint32_t *)B.flist, nf, (const uint32_t *)B.rep, (const unsigned long long *)B.best,
+               (const uint32_t *)B.winner, c->flag.p);
+  }
+  uint32_t n_tab64[64 * 16], adapt_word[ADAPT_WORDS] = {0, 0, 0, 0, 0, 0};
+  ELP_HIP(c, hipMemcpyAsync(n_tab64, B.n_table_dev, sizeof n_tab64, hipMemcpyDeviceToHost, st));
+  const bool adapt_read = c->derived.adapt_pending;
+  if (adapt_read) ELP_HIP(c, hipMemcpyAsync(adapt_word, c->adapt_err.p, sizeof adapt_word, hipMemcpyDeviceToHost, st));
+  ELP_HIP(c, elp::stream_wait(st));
+  if (adapt_read) adapt_note(c, adapt_word);
+  if (c->derived.adapt_bad_qual) return adapt_quality_error(c);  // computePhredScore panics on such a record (filters/mark-duplicates.go:64-66)
+  *n_tab_out = 0;
+  for (int k = 0; k < 64; k++) *n_tab_out += n_tab64[k * 16];
+  return 0;
+}
+
+// ---- mates, unless the front pass's neighbour pairs stand (MatePlan::fast).  (A pass that partitions the candidates by hash bits into
+// LDS tables was measured no faster on shuffled input: both are bound by the ~10 random loads of the key comparison every pair needs
+// once - two names, their offsets, read group -> library, split -, not by the insert.)  *big: some key has more than two records
+static int md_mates(elp_ctx *c, const MdSizes &S, const MdBufs &B, const MatePlan &P, uint32_t n_tab, bool *big) {
+  hipStream_t st = c->stream;
+  const uint64_t n = S.n;
+  ELP_HIP(c, hipMemsetAsync(c->mate.p, 0xFF, n * sizeof(uint32_t), st));  // (rep_of = pair_win is all EMPTY from the front pass)
+  if (n_tab) ELP_LAUNCH(c, "md_bloom_coarse", k_bloom_coarse, dim3(S.coarse_grid), dim3(256), 0, (const uint32_t *)B.bloom, (uint32_t)(S.bw / 16), B.coarse);
+  uint32_t e[4] = {0, 0, 0, 0};
+  for (uint64_t Tm = P.Tm;; Tm = S.T) {
+    ELP_HIP(c, hipMemsetAsync(B.table, 0xFF, Tm * sizeof(uint32_t), st));
+    ELP_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B.np_dev), (int)(uint32_t)P.nfixed, 1, st));
+    if (P.listed) ELP_HIP(c, hipMemsetAsync(B.n_table_dev, 0, 64 * 16 * sizeof(uint32_t), st));  // (read back already: now the lists' lengths)
+    ELP_LAUNCH(c, "md_mate_pairs", k_mate_pairs, dim3(S.mate_grid), dim3(256), 0, B.m, (const uint4 *)B.fkey, B.code, (const uint32_t *)B.hash32, (const uint32_t *)B.hash_lo,
+               (const uint32_t *)B.bloom, (uint32_t)(S.bw - 1), (const uint32_t *)(n_tab ? B.coarse : nullptr), B.table, Tm - 1, c->mate.p, B.rep_of, c->err_flag.p, P.fixed ? 1 : 0, B.pk,
+               B.pv, P.listed ? B.tab_list : (uint32_t *)nullptr, B.n_table_dev, S.tab_cap);
+    if (P.listed)
+      ELP_LAUNCH(c, "md_mate_table", k_mate_table, dim3(blocks_for(P.list_n, 256)), dim3(256), 0, B.m, (const uint4 *)B.fkey, (const uint8_t *)B.code, (const uint32_t *)B.hash32,
+                 (const uint32_t *)B.hash_lo, (const uint32_t *)B.tab_list, (const uint32_t *)B.n_table_dev, S.tab_cap, B.table, Tm - 1, c->mate.p, B.rep_of, c->err_flag.p);
+    ELP_TRY(fetch_err(c, e));
+    if (!(e[1] & 2u)) break;
+    if (Tm == S.T) return set_error(c, ELP_ERR_HIP, "mark duplicates: mate table overflow");
+    // more Bloom-filter hits than estimated: once more with the full-size table (the look-ups and entries are simply made again)
+    ELP_HIP(c, hipMemsetAsync(c->err_flag.p + 1, 0, 4, st));
+    ELP_HIP(c, hipMemsetAsync(c->mate.p, 0xFF, n * sizeof(uint32_t), st));
+    ELP_HIP(c, hipMemsetAsync(B.rep_of, 0xFF, n * sizeof(uint32_t), st));
+  }
+  *big = e[1] != 0;
+  return 0;
+}
+
+// ---- big groups: keys with more than two records pair their members up in arrival order
+static int md_big_groups(elp_ctx *c, const MdSizes &S, const MdScratch &L, const MdBufs &B) {
+  hipStream_t st = c->stream;
+  ELP_HIP(c, hipMemsetAsync(c->err_flag.p + 1, 0, 4, st));
+  uint64_t *bk, *ks;
+  uint32_t *bv, *vs, *cnt_dev = c->err_flag.p + 3;  // the scan-total mailbox doubles as the list counter
+  ELP_TRY(scratch(c, 2, L.big, &bk));  // `best` and `winner` of the fragment phase are free (MdScratch: the one regrowth in mid-call)
+  ELP_TRY(scratch(c, 3, L.big, &bv));
+  ELP_HIP(c, hipMemsetAsync(cnt_dev, 0, 4, st));
+  ELP_LAUNCH(c, "md_big_collect", k_big_collect, dim3(S.grid), dim3(256), 0, S.n, (const uint32_t *)B.rep_of, c->mate.p, bk, bv, cnt_dev);
+  uint32_t cnt = 0;
+  ELP_HIP(c, hipMemcpyAsync(&cnt, cnt_dev, 4, hipMemcpyDeviceToHost, st));
+  ELP_HIP(c, elp::stream_wait(st));
+  ELP_HIP(c, hipMemsetAsync(cnt_dev, 0, 4, st));
+  ProfScope ps(c, "md_big_");
+  ELP_TRY(radix_sort_pairs(c, bk, bv, bk + S.n, bv + S.n, cnt, &ks, &vs));
+  ELP_LAUNCH(c, "md_big_pair", k_big_pair, dim3(blocks_for(cnt, 256)), dim3(256), 0, cnt, (const uint64_t *)ks, c->mate.p);
+  return 0;
+}
+
+// ---- pairs: the entries of the pairs that formed in the table, partition by hash bits, one LDS table per bucket
+static int md_pairs(elp_ctx *c, const MdSizes &S, const MdScratch &L, const MdBufs &B, const MatePlan &P) {
+  hipStream_t st = c->stream;
+  uint32_t *bounds;
+  ELP_TRY(scratch(c, 1, L.bounds_words, &bounds));  // `rep` and the fragment list are free again
+  // with radix passes in front, the last of them reports the buckets' bounds (RadixBounds: both arrays start as 0xFF..); a list that is
+  // one bucket (tiny inputs) takes its bounds from k_pair_bounds
+  const bool folded = S.ndig > 0;
+  ELP_HIP(c, hipMemsetAsync(bounds, folded ? 0xFF : 0, 2 * S.nb * sizeof(uint32_t), st));
+  // fast: nothing went through the mate table - `rep_of` (pair_win's buffer) is still all EMPTY from the front pass and no owner carries
+  // MC_TABBED: no second fill, no scan of the codes
+  if (!P.fast) {
+    ELP_HIP(c, hipMemsetAsync(c->pair_win.p, 0xFF, S.n * sizeof(uint32_t), st));
+    if (P.listed)
+      ELP_LAUNCH(c, "md_pair_list", k_pair_list_lists, dim3(blocks_for(P.list_n, 256 * PL_TILES)), dim3(256), 0, B.m, (const uint4 *)B.fkey, (const uint32_t *)c->mate.p, (const uint32_t *)B.tab_list,
+                 (const uint32_t *)B.n_table_dev, S.tab_cap, B.pk, B.pv, B.np_dev);
+    else
+      ELP_LAUNCH(c, "md_pair_list", k_pair_list_table, dim3(S.list_grid), dim3(256), 0, B.m, (const uint4 *)B.fkey, (const uint32_t *)c->mate.p, (const uint8_t *)B.code, B.pk, B.pv,
+                 B.np_dev);
+  }
+  uint64_t *ks = B.pk;
+  uint32_t *vs = B.pv;
+  if (folded) {
+    ProfScope ps(c, "md_pair_");
+    ELP_TRY(radix_sort_pairs_low(c, B.pk, B.pv, B.pk + S.npmax, B.pv + S.npmax, S.npmax, S.ndig, &ks, &vs, nullptr, false, B.np_dev,
+                                 RadixBounds{bounds, bounds + S.nb, (uint32_t)((1ull << S.sbits) - 1ull), S.sbits - S.bbits}));
+  } else {
+    ELP_LAUNCH(c, "md_pair_bounds", k_pair_bounds, dim3(S.bounds_grid), dim3(256), 0, (const uint64_t *)ks, (const uint32_t *)B.np_dev, S.sbits, S.bbits, bounds, bounds + S.nb);
+  }
+  ELP_LAUNCH(c, "md_pair_bucket", k_pair_bucket, dim3((unsigned)S.nb), dim3(PB_THREADS), 0, B.m, (const uint4 *)B.fkey, (const uint32_t *)c->mate.p, (const uint64_t *)ks, vs,
+             (const uint32_t *)bounds, (const uint32_t *)(bounds + S.nb), std::min(c->tune.pair_table_slots, PB_CAP), c->pair_win.p, c->flag.p, folded ? 1 : 0);
+  return 0;
 }
 
 static int markdup_impl(elp_ctx *c) {
@@ -921,193 +1086,26 @@ static int markdup_impl(elp_ctx *c) {
   const bool fuse_adapt = !c->derived.adapted();  // (keys or scores missing: the fused pass writes both)
   int pos_bits = 1;
   if (fuse_adapt) ELP_TRY(adapt_begin(c, &pos_bits));
-  else ELP_TRY(ensure_adapted(c, false));  // (its quality-error word is read with this call's first read-back, below)
-  const unsigned grid = blocks_for(n, 256);
-  hipStream_t st = c->stream;
-  MdCols m{n, c->refid.p, c->flag.p, c->rgid.p, c->rg_lib.p, c->split.p, c->upos.p, c->score.p, c->qname_off.p, c->qname.p};
-  const uint64_t T = table_size_for(n);
-  uint32_t *table;
-  ELP_TRY(scratch(c, 0, T, &table));
-  uint32_t *rep;
-  unsigned long long *best;
-  ELP_TRY(scratch(c, 2, n + 16, &best));  // (sized for the pair phase's list as well: no reallocation in mid-call)
-  uint32_t *winner;
-  ELP_TRY(scratch(c, 3, n + 16, &winner));
-
-  uint4 *fkey;
-  ELP_TRY(scratch(c, 5, n + 8, &fkey));
-  // keys of all records + the list of true fragments (in `rep`'s scratch slot behind the n entries of frep)
-  ELP_TRY(ensure(c, c->md_ctr, 16 + 64 * 16));
-  uint32_t *nf_dev = c->md_ctr.p;
-  ELP_TRY(scratch(c, 1, 2 * n + 16, &rep));
-  uint32_t *flist = rep + n + 8;
-  ELP_HIP(c, hipMemsetAsync(c->md_ctr.p, 0, (16 + 64 * 16) * sizeof(uint32_t), st));  // every counter of this call in one fill
-  FrontCols fc{n, c->refid.p, c->pos.p, c->flag.p, c->has_sr.p, c->rgid.p, c->rg_lib.p, c->split.p, c->cigar_off.p, c->cigar.p, c->qname_off.p, c->qname.p,
-               (uint32_t)c->n_ref, pos_bits};
-  // the list's length comes back through the mailbox while the stream runs on (the score kernel, when the adapt stage is this call's)
-  ELP_TRY(mailbox(c));
-  ELP_LAUNCH(c, "md_frag_list", k_frag_list, dim3(std::min<unsigned>(blocks_for(n, FLI_CHUNK), (unsigned)c->n_cu * 8)), dim3(256), 0, fc, fkey, flist, nf_dev, best, winner);
-  ELP_HIP(c, hipMemcpyAsync(c->mail, nf_dev, 4, hipMemcpyDeviceToHost, st));
-  ELP_HIP(c, hipEventRecord(c->mail_ev, st));
+  else ELP_TRY(ensure_adapted(c, false));  // (its quality-error word is read with this call's first read-back, md_fragments)
+  const MdSizes S(n);
+  const MdScratch L(S);
+  MdBufs B;
+  ELP_TRY(md_carve(c, L, &B));
+  const FrontCols fc{n, c->refid.p, c->pos.p, c->flag.p, c->has_sr.p, c->rgid.p, c->rg_lib.p, c->split.p, c->cigar_off.p, c->cigar.p, c->qname_off.p, c->qname.p,
+                     (uint32_t)c->n_ref, pos_bits};
+  ELP_TRY(md_frag_list(c, S, B, fc));
   if (fuse_adapt) ELP_TRY(adapt_scores(c));
-
-  // the pair phase's list, partitioned by hash bits: at most n / 2 pairs
-  int bbits = 0;
-  while (bbits < 24 && ((n / 2 + 1) >> bbits) > (uint64_t)PB_TARGET) bbits++;
-  const int ndig = (bbits + 7) / 8, sbits = 8 * ndig;
-  const size_t nb = (size_t)1 << bbits;
-  uint32_t *np_dev = c->md_ctr.p + 1;
-
-  // ---- mates (+ the pairs' fragment look-ups and the entries of the neighbour pairs)
-  uint64_t bw = 1024;  // Bloom filter words: ~2 bits per record, at most 4 MiB (what one XCD's L2 holds)
-  while (bw < n / 16 && bw < (1u << 20)) bw <<= 1;
-  uint32_t *bloom, *hash32;
-  uint8_t *code;
-  const uint32_t tab_cap = (uint32_t)((blocks_for(n, 256 * MP_R) + 63) / 64) * 256u * MP_R;  // a list's share of the workgroups x their records
-  ELP_TRY(scratch(c, 6, bw + bw / 512 + 16 + n + 16 + (n + 16) / 4 + 64 * (size_t)tab_cap + 16 + n + 16, &bloom));
-  uint32_t *coarse = bloom + bw;  // one bit per 16 words of the filter
-  hash32 = coarse + bw / 512 + 16;
-  code = reinterpret_cast<uint8_t *>(hash32 + n + 8);
-  uint32_t *tab_list = hash32 + n + 16 + (n + 16) / 4;  // k_mate_pairs' deferred table inserts (aligner order): 64 lists
-  uint32_t *hash_lo = tab_list + 64 * (size_t)tab_cap + 8;  // the low half of the key hashes (hash32: the high half)
-  uint32_t *rep_of = c->pair_win.p;  // free until the pair phase fills it
-  uint32_t *n_table_dev = c->md_ctr.p + 16;  // 64 counters, 16 words apart
-  ELP_HIP(c, hipMemsetAsync(bloom, 0, bw * sizeof(uint32_t), st));
-  uint32_t n_tab = 0, n_tab64[64 * 16];
-  uint32_t adapt_word[ADAPT_WORDS] = {0, 0, 0, 0, 0, 0};
-  // the fragments' table first: it is final before any pair looks its key up
-  ELP_HIP(c, elp::event_wait(c->mail_ev));
-  const uint32_t nf = c->mail[0];
-  const unsigned fgrid = blocks_for(nf, 256);
-  const uint64_t Tf = nf ? std::min<uint64_t>(T, table_size_for(4ull * nf)) : 0;  // sparse: most look-ups of the pairs end at an empty slot
-  const uint64_t npmax = n + 2;  // (whatever the mates' order turns out to be)
-  uint64_t *pk;
-  ELP_TRY(scratch(c, 7, 2 * npmax + (2 * npmax + Tf + Tf / 32 + 64) / 2 + 8, &pk));
-  uint32_t *pv = reinterpret_cast<uint32_t *>(pk + 2 * npmax), *ftable = pv + 2 * npmax, *fbits = ftable + Tf;
-  if (nf) {
-    ELP_HIP(c, hipMemsetAsync(ftable, 0xFF, Tf * sizeof(uint32_t), st));
-    ELP_LAUNCH(c, "md_frag_insert", k_frag_insert, dim3(fgrid), dim3(256), 0, m, (const uint4 *)fkey, (const uint32_t *)flist, nf, ftable, Tf - 1, rep, best);
-    ELP_LAUNCH(c, "md_frag_bits", k_frag_bits, dim3(blocks_for(Tf / 32, 256)), dim3(256), 0, (const uint32_t *)ftable, Tf / 32, fbits);
-  }
-  const int optimistic = c->tune.mate_path == 0;
-  const uint32_t nfx = (uint32_t)((n + 1) / 2);
-  if (fuse_adapt)
-    ELP_LAUNCH(c, "md_front", k_md_front<true>, dim3(blocks_for(n, MF_RECS)), dim3(MF_THREADS), 0, fc, (const int32_t *)c->score.p, c->upos.p, c->key.p, fkey, code, hash32, hash_lo, bloom,
-               (uint32_t)(bw - 1), n_table_dev, (const uint32_t *)ftable, (const uint32_t *)fbits, nf ? Tf - 1 : (uint64_t)0, best, c->mate.p, c->pair_win.p, pk, pv,
-               np_dev, nfx, optimistic);
-  else
-    ELP_LAUNCH(c, "md_front", k_md_front<false>, dim3(blocks_for(n, MF_RECS)), dim3(MF_THREADS), 0, fc, (const int32_t *)c->score.p, c->upos.p, c->key.p, fkey, code, hash32, hash_lo, bloom,
-               (uint32_t)(bw - 1), n_table_dev, (const uint32_t *)ftable, (const uint32_t *)fbits, nf ? Tf - 1 : (uint64_t)0, best, c->mate.p, c->pair_win.p, pk, pv,
-               np_dev, nfx, optimistic);
+  uint32_t nf = 0, n_tab = 0;
+  ELP_TRY(md_front(c, S, L, B, fc, fuse_adapt, &nf));
   if (fuse_adapt) c->derived.keys = c->derived.scores = true;
   // elp_sort_ahead: the keys exist - the coordinate sort's key passes go to the sort lane now and run under the pair phase
   ELP_TRY(sort_presort(c));
-  // tournament among the fragments of pair-free groups (the pair bits are complete): queued in front of the read-back
-  if (nf) {
-    ELP_LAUNCH(c, "md_frag_tie", k_frag_tie, dim3(fgrid), dim3(256), 0, m, (const uint32_t *)flist, nf, (const uint32_t *)rep,
-               (const unsigned long long *)best, winner);
-    ELP_LAUNCH(c, "md_frag_flag", k_frag_flag, dim3(fgrid), dim3(256), 0, m, (const uint32_t *)flist, nf, (const uint32_t *)rep,
-               (const unsigned long long *)best, (const uint32_t *)winner, c->flag.p);
-  }
-  // the table only has to hold the records that are not exactly-two-neighbours (few in aligner order) plus the neighbour pairs a
-  // Bloom-filter hit sends there (at most as many again, in practice a fraction): size it by their number, not by n
-  ELP_HIP(c, hipMemcpyAsync(n_tab64, n_table_dev, sizeof n_tab64, hipMemcpyDeviceToHost, st));
-  const bool adapt_read = c->derived.adapt_pending;
-  if (adapt_read) ELP_HIP(c, hipMemcpyAsync(adapt_word, c->adapt_err.p, sizeof adapt_word, hipMemcpyDeviceToHost, st));
-  ELP_HIP(c, elp::stream_wait(st));
-  if (adapt_read) adapt_note(c, adapt_word);
-  if (c->derived.adapt_bad_qual) return adapt_quality_error(c);  // computePhredScore panics on such a record (filters/mark-duplicates.go:64-66)
-  for (int k = 0; k < 64; k++) n_tab += n_tab64[k * 16];
-
-  // aligner order (few candidates need a table): the neighbour pairs' entries go to fixed slots, the table's pairs behind them.  Else
-  // (coordinate-ordered, shuffled input, or mate_path = 2) every candidate goes through the table in HBM.  (A pass that partitions the
-  // candidates by hash bits into LDS tables was measured no faster on shuffled input: both are bound by the ~10 random loads of the key
-  // comparison every pair needs once - two names, their offsets, read group -> library, split -, not by the insert.)
-  const bool fixed = (uint64_t)n_tab < n / 8 && c->tune.mate_path == 0;
-  const uint64_t nfixed = fixed ? (n + 1) / 2 : 0;
-  // nobody announced a key: the front pass's neighbour pairs stand (mates, entries at their fixed slots, pair_win all EMPTY)
-  const bool fast = fixed && n_tab == 0;
-  if (!fast) ELP_HIP(c, hipMemsetAsync(c->mate.p, 0xFF, n * sizeof(uint32_t), st));  // (rep_of = pair_win is all EMPTY from the front pass)
-  if (n_tab && !fast) ELP_LAUNCH(c, "md_bloom_coarse", k_bloom_coarse, dim3(blocks_for(bw / 16, 256)), dim3(256), 0, (const uint32_t *)bloom, (uint32_t)(bw / 16), coarse);
-
-  uint64_t Tm = fixed ? std::min<uint64_t>(T, table_size_for(std::min<uint64_t>(n, 4ull * n_tab + 1024))) : T;
-  uint32_t e[4] = {0, 0, 0, 0};
-  // aligner order with a few records on the table path: their inserts are listed and made by a dense pass (the front pass's counters,
-  // read back above, serve as the lists' lengths)
-  const bool listed = fixed && n_tab != 0;
-  while (!fast) {
-    ELP_HIP(c, hipMemsetAsync(table, 0xFF, Tm * sizeof(uint32_t), st));
-    ELP_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(np_dev), (int)(uint32_t)nfixed, 1, st));
-    if (listed) ELP_HIP(c, hipMemsetAsync(n_table_dev, 0, 64 * 16 * sizeof(uint32_t), st));
-    ELP_LAUNCH(c, "md_mate_pairs", k_mate_pairs, dim3(blocks_for(n, 256 * MP_R)), dim3(256), 0, m, (const uint4 *)fkey, code,
-               (const uint32_t *)hash32, (const uint32_t *)hash_lo, (const uint32_t *)bloom, (uint32_t)(bw - 1), (const uint32_t *)(n_tab ? coarse : nullptr), table, Tm - 1, c->mate.p,
-               rep_of, c->err_flag.p, fixed ? 1 : 0, pk, pv, listed ? tab_list : (uint32_t *)nullptr, n_table_dev, tab_cap);
-    if (listed)  // (the lists hold the records the front pass counted plus the neighbour pairs a filter hit sent along: in practice a fraction as many again)
-      ELP_LAUNCH(c, "md_mate_table", k_mate_table, dim3(blocks_for(std::min<uint64_t>(n, 2ull * n_tab + 4096), 256)), dim3(256), 0, m, (const uint4 *)fkey, (const uint8_t *)code,
-                 (const uint32_t *)hash32, (const uint32_t *)hash_lo, (const uint32_t *)tab_list, (const uint32_t *)n_table_dev, tab_cap, table, Tm - 1, c->mate.p, rep_of,
-                 c->err_flag.p);
-    ELP_TRY(fetch_err(c, e));
-    if (!(e[1] & 2u)) break;
-    if (Tm == T) return set_error(c, ELP_ERR_HIP, "mark duplicates: mate table overflow");
-    Tm = T;  // more Bloom-filter hits than estimated: once more with the full-size table (the look-ups and entries are simply made again)
-    ELP_HIP(c, hipMemsetAsync(c->err_flag.p + 1, 0, 4, st));
-    ELP_HIP(c, hipMemsetAsync(c->mate.p, 0xFF, n * sizeof(uint32_t), st));
-    ELP_HIP(c, hipMemsetAsync(rep_of, 0xFF, n * sizeof(uint32_t), st));
-  }
-  if (e[1]) {
-    // keys with more than two records: pair their members up in arrival order
-    ELP_HIP(c, hipMemsetAsync(c->err_flag.p + 1, 0, 4, st));
-    uint64_t *bk;
-    uint32_t *bv, *cnt_dev = c->err_flag.p + 3;  // the scan-total mailbox doubles as the list counter
-    ELP_TRY(scratch(c, 2, 2 * n + 8, &bk));  // `best` and `winner` of the fragment phase are free
-    ELP_TRY(scratch(c, 3, 2 * n + 8, &bv));
-    ELP_HIP(c, hipMemsetAsync(cnt_dev, 0, 4, st));
-    ELP_LAUNCH(c, "md_big_collect", k_big_collect, dim3(grid), dim3(256), 0, n, (const uint32_t *)rep_of, c->mate.p, bk, bv, cnt_dev);
-    uint32_t cnt = 0;
-    ELP_HIP(c, hipMemcpyAsync(&cnt, cnt_dev, 4, hipMemcpyDeviceToHost, st));
-    ELP_HIP(c, elp::stream_wait(st));
-    ELP_HIP(c, hipMemsetAsync(cnt_dev, 0, 4, st));
-    uint64_t *ks;
-    uint32_t *vs;
-    ProfScope ps(c, "md_big_");
-    ELP_TRY(radix_sort_pairs(c, bk, bv, bk + n, bv + n, cnt, &ks, &vs));
-    ELP_LAUNCH(c, "md_big_pair", k_big_pair, dim3(blocks_for(cnt, 256)), dim3(256), 0, cnt, (const uint64_t *)ks, c->mate.p);
-  }
-
-  // ---- pairs: the entries of the pairs that formed in the table, partition by hash bits, one LDS table per bucket
-  {
-    uint32_t *bounds;
-    ELP_TRY(scratch(c, 1, 2 * nb + 8, &bounds));  // `frep` and the fragment list are free again
-    // with radix passes in front, the last of them reports the buckets' bounds (RadixBounds: both arrays start as 0xFF..); a list that is
-    // one bucket (tiny inputs) takes its bounds from k_pair_bounds
-    const bool folded = ndig > 0;
-    ELP_HIP(c, hipMemsetAsync(bounds, folded ? 0xFF : 0, 2 * nb * sizeof(uint32_t), st));
-    // aligner order without stragglers: no record announced its key, so nothing went through the mate table - `rep_of` (pair_win's
-    // buffer) is still all EMPTY from the front pass and no owner carries MC_TABBED: no second fill, no scan of the codes
-    const bool no_table = fixed && n_tab == 0 && !e[1];
-    if (!no_table) {
-      ELP_HIP(c, hipMemsetAsync(c->pair_win.p, 0xFF, n * sizeof(uint32_t), st));
-      if (listed)
-        ELP_LAUNCH(c, "md_pair_list", k_pair_list_lists, dim3(blocks_for(std::min<uint64_t>(n, 2ull * n_tab + 4096), 256 * PL_TILES)), dim3(256), 0, m, (const uint4 *)fkey,
-                   (const uint32_t *)c->mate.p, (const uint32_t *)tab_list, (const uint32_t *)n_table_dev, tab_cap, pk, pv, np_dev);
-      else
-        ELP_LAUNCH(c, "md_pair_list", k_pair_list_table, dim3(blocks_for(n, 256 * PL_TILES)), dim3(256), 0, m, (const uint4 *)fkey, (const uint32_t *)c->mate.p,
-                   (const uint8_t *)code, pk, pv, np_dev);
-    }
-    uint64_t *ks = pk;
-    uint32_t *vs = pv;
-    if (ndig) {
-      ProfScope ps(c, "md_pair_");
-      ELP_TRY(radix_sort_pairs_low(c, pk, pv, pk + npmax, pv + npmax, npmax, ndig, &ks, &vs, nullptr, false, np_dev,
-                                   RadixBounds{bounds, bounds + nb, (uint32_t)((1ull << sbits) - 1ull), sbits - bbits}));
-    }
-    if (!folded)
-      ELP_LAUNCH(c, "md_pair_bounds", k_pair_bounds, dim3(blocks_for(npmax, 256)), dim3(256), 0, (const uint64_t *)ks, (const uint32_t *)np_dev, sbits, bbits,
-                 bounds, bounds + nb);
-    ELP_LAUNCH(c, "md_pair_bucket", k_pair_bucket, dim3((unsigned)nb), dim3(PB_THREADS), 0, m, (const uint4 *)fkey, (const uint32_t *)c->mate.p,
-               (const uint64_t *)ks, vs, (const uint32_t *)bounds, (const uint32_t *)(bounds + nb), std::min(c->tune.pair_table_slots, PB_CAP), c->pair_win.p, c->flag.p,
-               folded ? 1 : 0);
-  }
+  ELP_TRY(md_fragments(c, B, nf, &n_tab));
+  const MatePlan P = mate_plan(n, n_tab, c->tune.mate_path, S.T);
+  bool big = false;
+  if (!P.fast) ELP_TRY(md_mates(c, S, B, P, n_tab, &big));
+  if (big) ELP_TRY(md_big_groups(c, S, L, B));
+  ELP_TRY(md_pairs(c, S, L, B, P));
   c->radix_check_pending = true;
   c->derived.marked = true;
   return 0;

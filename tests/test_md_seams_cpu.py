@@ -18,7 +18,7 @@ def _csrc(name):
 
 
 def test_geometry_constants_are_the_kernels():
-    src = _csrc("markdup.hip")
+    src = _csrc("markdup_plan.hpp")  # (the constants the launch plan shares with the kernels)
     assert re.search(r"MF_THREADS = 320, MF_RECS = (\d+);", src).group(1) == str(ms.WG)
     assert re.search(r"MAX_QNAME = (\d+);", _csrc("common.hpp")).group(1) == str(ms.MAX_QNAME) == str(ms.LENGTHS[-1])
     for motif, (p, _) in ms.MOTIFS.items():
