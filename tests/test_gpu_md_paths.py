@@ -2,8 +2,8 @@
 (tests/md_paths.py): the duplicate flags bit for bit against the oracle - compared as the seam tests compare them - and, from the
 profile's launch counts, the kernels that must and must not have run, which proves that the path was the one meant.
 
-Not reached by any test: the mate table's overflow retry (more Bloom-filter hits than the first table was sized for); nobody has an
-input for it."""
+The mate table's overflow retry (more Bloom-filter hits than the first table was sized for) needs an input derived from the key hash:
+tests/test_gpu_md_bloom.py."""
 import numpy as np
 import pytest
 
