@@ -30,7 +30,7 @@ HIP_SYMBOLS = [
     "elp_set_read_group_ids", "elp_pinned_alloc", "elp_pinned_free", "elp_stage_bam", "elp_emit_sorted_bam", "elp_stage_bgzf", "elp_emit_sorted_bgzf",
     "elp_set_header_columns", "elp_stage_columns", "elp_set_read_group_ids_flat", "elp_filter_records_flat", "elp_group_probe", "elp_group_init_transport", "elp_copy_records", "elp_exchange_records", "elp_group_set_p2p", "elp_group_share", "elp_emit_merged_bam", "elp_bqsr_lut_upload",
     "elp_order_keep", "elp_emit_merged_bgzf", "elp_emit_concat_bam", "elp_emit_concat_bgzf",
-    "elp_set_reference_names_flat", "elp_emit_sorted_sam", "elp_emit_merged_sam", "elp_emit_concat_sam",
+    "elp_set_reference_names_flat", "elp_emit_sorted_sam", "elp_emit_merged_sam", "elp_emit_concat_sam", "elp_stage_sam",
     "elp_snapshot", "elp_rollback", "elp_set_tuning", "elp_profile_enable", "elp_profile_reset", "elp_profile_count", "elp_profile_get", "elp_debug_check_guards",
 ]
 HOST_SYMBOLS = [
@@ -138,7 +138,8 @@ def hip() -> C.CDLL:
         for name, args in (("elp_set_reference_names_flat", [C.c_void_p, C.c_void_p, C.c_void_p]),
                            ("elp_emit_sorted_sam", [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
                            ("elp_emit_merged_sam", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
-                           ("elp_emit_concat_sam", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)])):
+                           ("elp_emit_concat_sam", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+                           ("elp_stage_sam", [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint16])):
             if ELP_AB_BUILD and not hasattr(L, name):
                 continue
             getattr(L, name).argtypes = args

@@ -191,15 +191,7 @@ __global__ __launch_bounds__(256) void k_bam_out_sizes(BamOut m, BamOut m2, cons
   sizes[j] = out_size<OPT>(mm, i, &e);
   if (e) atomicOr(err, e);
 }
-// Alignment.bin(), sam/bam-files.go:443-468
-__device__ inline uint32_t reg2bin(int32_t beg, int32_t end) {
-  if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
-  if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
-  if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
-  if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
-  if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
-  return 0;
-}
+// (Alignment.bin(): reg2bin / record_bin, bamout.hpp)
 // one wavefront per output record; `out` = this chunk's buffer, offs = exclusive scan of the chunk's sizes
 template <bool OPT>
 __global__ __launch_bounds__(256) void k_bam_out_emit(BamOut m_first, BamOut m_second, const uint32_t *__restrict__ src, uint64_t k0, uint32_t cnt,
@@ -220,19 +212,18 @@ __global__ __launch_bounds__(256) void k_bam_out_emit(BamOut m_first, BamOut m_s
     if (lane == 0) {
       const uint16_t f = m.flag[i];
       const int32_t beg = m.pos[i] - 1;
-      int32_t e2 = beg;
+      uint32_t ref_span = 0;
       if (!(f & F_UNMAPPED)) {
         for (uint32_t k = 0; k < n_cig; k++) {
           const uint32_t c = m.cigar[c0 + k];
-          if (op_consumes_ref(c & 0xF)) e2 += (int32_t)(c >> 4);
+          if (op_consumes_ref(c & 0xF)) ref_span += c >> 4;
         }
-        e2--;
       }
       st_u32(o + 4, (uint32_t)m.refid[i]);
       st_u32(o + 8, (uint32_t)beg);
       o[12] = (uint8_t)l_name;
       o[13] = m.mapq[i];
-      st_u16(o + 14, reg2bin(beg, e2));
+      st_u16(o + 14, record_bin(f, beg, ref_span));
       st_u16(o + 16, n_cig);
       st_u16(o + 18, f);
       st_u32(o + 20, l_seq);

@@ -37,6 +37,22 @@ __device__ __forceinline__ const BamOut &out_source(const BamOut &m, const BamOu
   return mm;
 }
 
+// Alignment.bin(), sam/bam-files.go:443-468
+__device__ inline uint32_t reg2bin(int32_t beg, int32_t end) {
+  if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
+  if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
+  if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
+  if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
+  if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
+  return 0;
+}
+// ... of a record with this FLAG whose POS - 1 is beg and whose reference-consuming CIGAR operations add up to ref_span (int32 arithmetic
+// that wraps, as the reference's).  The BAM emitter (bam.hip) and SAM text in (samin.hip) write the bin field with it.
+__device__ inline uint32_t record_bin(uint16_t flag, int32_t beg, uint32_t ref_span) {
+  const int32_t end = (flag & F_UNMAPPED) ? beg : (int32_t)((uint32_t)beg + ref_span - 1u);
+  return reg2bin(beg, end);
+}
+
 // SAM text (sam.hip): the @SQ SN strings of the stream's dictionary (elp_set_reference_names_flat), name of refid r = names[name_off[r] ..
 // name_off[r + 1]).  A stream of two contexts has ONE table: both hold equal names (checked, as for the tag filter).
 struct SamNames {

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "samparse.hpp"
 
 namespace elp {
 
@@ -46,19 +47,8 @@ __device__ inline long long tag_int_value(uint8_t t, const uint8_t *p) {
     default: return (long long)ld_u32(p);
   }
 }
-// formatBamTag's integer rule (:492-525): type and size of the re-encoded value
-__device__ inline uint32_t int_out(long long v, uint8_t *type) {
-  if (v < 0) {
-    if (v >= -128) { *type = 'c'; return 1; }
-    if (v >= -32768) { *type = 's'; return 2; }
-    *type = 'i';
-    return 4;
-  }
-  if (v <= 255) { *type = 'C'; return 1; }
-  if (v <= 65535) { *type = 'S'; return 2; }
-  *type = 'I';
-  return 4;
-}
+// formatBamTag's integer rule (:492-525): type and size of the re-encoded value (samparse.hpp's, which SAM text in stores by)
+__device__ __forceinline__ uint32_t int_out(long long v, uint8_t *type) { return samparse::int_store((int64_t)v, type); }
 
 // a two-byte key as the 16-bit number the tag filter's bit table is indexed by
 __device__ __forceinline__ uint32_t tag_key(const uint8_t *t) { return (uint32_t)t[0] | ((uint32_t)t[1] << 8); }

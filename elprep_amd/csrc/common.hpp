@@ -194,6 +194,11 @@ struct elp_ctx {
   std::vector<uint32_t> h_ref_names_off;
   uint32_t max_ref_name = 0;
   bool have_ref_names = false;
+  // elp_stage_sam (samin.hip): RNAME / RNEXT -> refid, an open-addressing table over ref_names (slot = refid + 1, 0 = empty; a power of
+  // two of slots, at least twice the names).  Made by the first elp_stage_sam behind the names; leaves with them (have_ref_names = false)
+  elp::DVec<uint32_t> ref_name_slots;
+  uint32_t ref_name_mask = 0;
+  bool have_ref_name_table = false;
   // optional-field settings of a run (bam.hip: elp_set_tag_filter, elp_set_replace_read_group); elp_reset and elp_set_header clear both
   static constexpr size_t TAG_WORDS = 65536 / 32;
   bool tag_filter = false;             // tag_drop holds a table: bit k of it = fields with the 16-bit key k do not go out
@@ -264,6 +269,7 @@ struct elp_ctx {
     int tie_rounds = 0;        // 1: the sort's long runs by LSD rounds over every live position (no key-then-compare shortcut)
     int exchange_piece = 0;    // > 0: records per piece of elp_exchange_records (tests: several pieces on small inputs)
     int emit_pass = 0;         // > 0: at most this many records per pass of the BAM / BGZF emitters (tests: several passes on small inputs)
+    int sam_pass = 0;          // > 0: at most this many lines per write pass of elp_stage_sam (tests: several passes on small inputs)
     long long bgzf_inflate_piece = 2ll << 30;  // elp_stage_bgzf: inflated bytes whose blocks are decoded by one launch (token scratch: 2.7x that)
     int bgzf_copy_chunk = 0;   // elp_stage_bgzf: blocks per H2D chunk / decoder launch (0: what fills the chip once)
     int bgzf_tok_lds = 0;      // (experiments) unused dynamic LDS bytes per decoder wave: lowers the waves per CU

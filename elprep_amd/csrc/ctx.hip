@@ -257,6 +257,7 @@ int install_dictionary(elp_ctx *c, int32_t n_ref, const int32_t *ref_len) {
   c->n_ref = n_ref;
   c->h_ref_len = len;
   c->have_ref_names = false;  // (the names belong to the dictionary that leaves)
+  c->have_ref_name_table = false;
   if (n_ref) ELP_HIP(c, hipMemcpyAsync(c->ref_len.p, c->h_ref_len.data(), (size_t)n_ref * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   ELP_HIP(c, elp::stream_wait(c->stream));
   c->h_ref_seq.assign((size_t)n_ref, nullptr);
@@ -363,6 +364,7 @@ int elp_set_header(elp_ctx *c, const elp_header *h) {
   c->h_ref_len0 = c->h_ref_len;
   c->dict_replaced = false;
   c->have_ref_names = false;     // (the SAM emitters' names belong to the dictionary: the host sets the new header's)
+  c->have_ref_name_table = false;
   c->h_rg_lib.assign(h->rg_lib, h->rg_lib + h->n_rg);
   c->h_rg_cov.assign(h->rg_cov, h->rg_cov + h->n_rg);
   for (int i = 0; i < h->n_rg; i++) {
@@ -634,6 +636,7 @@ int elp_set_tuning(elp_ctx *c, const char *key, int64_t value) {
   else if (k == "sort_pairs") c->tune.sort_pairs = v;
   else if (k == "exchange_piece") c->tune.exchange_piece = v;
   else if (k == "emit_pass") c->tune.emit_pass = v;
+  else if (k == "sam_pass") c->tune.sam_pass = v;
   else if (k == "bgzf_stored") c->tune.bgzf_stored = v;
   else if (k == "bgzf_tok_fail_above") c->tune.bgzf_tok_fail_above = v;
   else if (k == "bgzf_fixed") c->tune.bgzf_fixed = v;

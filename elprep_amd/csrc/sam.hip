@@ -301,6 +301,7 @@ int elp_set_reference_names_flat(elp_ctx *c, const uint8_t *names, const uint32_
   c->h_ref_names_off.swap(off);
   c->max_ref_name = longest;
   c->have_ref_names = true;
+  c->have_ref_name_table = false;  // (elp_stage_sam's look-up is made from the names the first time it is asked for)
   return 0;
 }
 

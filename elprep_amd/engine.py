@@ -200,6 +200,14 @@ class Engine:
         bgzf = np.ascontiguousarray(bgzf, dtype=np.uint8)
         self._check(self.L.elp_stage_bgzf(self.h, _vp(bgzf), bgzf.size, first_record, split_id))
 
+    def stage_sam(self, text, split_id: int = 0):
+        """text: bytes or a uint8 array of whole alignment lines of a SAM file, the header lines stripped (page-locked memory is read in
+        place): parsed into BAM records on the device and staged as stage_bam stages them (elp_stage_sam).  RNAME / RNEXT are looked up
+        in the reference names: the header's are set first if none are"""
+        self._header_names()
+        d = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+        self._check(self.L.elp_stage_sam(self.h, _vp(d), d.size, split_id))
+
     def _emit_two(self, fn, spread: "Engine") -> np.ndarray:
         n = C.c_uint64()
         self._check(fn(self.h, spread.h, C.c_void_p(0), 0, C.byref(n)))

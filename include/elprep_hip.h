@@ -160,6 +160,47 @@ int elp_emit_sorted_bam(elp_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *n_by
  * size of the stored form, which is also the room `out` must offer; *n_bytes_out of the real call is the actual size. */
 int elp_stage_bgzf(elp_ctx *ctx, const uint8_t *bgzf, uint64_t n_bytes, uint64_t first_record, uint16_t split_id);
 int elp_emit_sorted_bgzf(elp_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out);
+/* ---- SAM text in (sam/sam-files.go:186-410, sam/string-scanner.go, ScanCigarString sam/sam-types.go:680-740; csrc/samin.hip) ----
+ * The reference reads SAM text whenever it is fed from an aligner's pipe (sam.Open picks the reader by content, sam/aln-files.go:144-174).
+ * elp_stage_sam replaces the host's parseSamAlignment per line + elp_stage: `text` = whole alignment lines of a SAM file - the host reads
+ * and strips the header lines, as it writes them for the emitters.  The device turns every line into the BAM record
+ * formatBamAlignment(parseSamAlignment(line)) writes behind AddREFID (filters/simple-filters.go:208-231) and stages it as elp_stage_bam
+ * stages records: columns, sr state, RG look-up and the staged bytes the emitters, the tag filter, elp_filter_exact_strict,
+ * elp_copy_records and elp_exchange_records read.  A staging call with elp_stage_bam's rules: it appends and returns when `text` may be
+ * reused; page-locked `text` is read in place, pageable text goes through the pinned double buffer; it may be mixed with elp_stage_bam /
+ * elp_stage_bgzf on one context, not with elp_stage; every record gets `split_id`.  Needs a header, the read-group ids
+ * (elp_set_read_group_ids*, unless elp_set_replace_read_group is in force) and the reference names (elp_set_reference_names_flat:
+ * ELP_ERR_ARG without them; RNAME and RNEXT are looked up in a hash table over them in HBM, made by the first call behind the names and
+ * dropped with them); refused behind elp_replace_reference_dictionary, as the other staging calls are.
+ *   A line is the bytes up to '\n' with one trailing '\r' dropped (bufio.ScanLines); a last line without '\n' counts; an empty line and
+ * a line of more than 1 MiB (maxTokenSize, sam/sam-files.go:614) are ELP_ERR_DATA.  Eleven mandatory fields (ten tabs, else
+ * ELP_ERR_DATA): FLAG = ParseUint(.., 16), MAPQ = ParseUint(.., 8), POS / PNEXT / TLEN = ParseInt(.., 32) (a sign is read by ParseInt
+ * only); BAM pos = POS - 1 with int32 wrap-around.  RNAME: "*" and "=" give -1 (AddREFID knows no contig "="), else the name's refid;
+ * RNEXT: "*" -1, "=" RNAME's refid.  CIGAR: "*" or empty = no operation, else <decimal><op> with op in "MIDNSHP=X" in either case
+ * (cigarOperationsTable), adjacent operations of one kind merged with their lengths added ("5M5M" is 10M).  SEQ: a nibble per byte from
+ * "=ACMGRSVTWYHKDBN", every other byte 15 (lower case, and "*" = ONE base N); QUAL: every byte - 33 modulo 256 ("*" = one quality of 9).
+ * Optional fields KK:T:value: A one byte; i = ParseInt(.., 64) stored in the smallest of c C s S i I that holds it (formatBamTag,
+ * sam/bam-files.go:492-523); Z the bytes + NUL; B a subtype, ',' and at least one entry, entries ParseInt at 8 / 32 bits (c, i) or
+ * ParseUint at 8 / 16 / 32 (C, S, I) - and B:s through ParseUint(.., 16) cast to int16 as the reference has it (:263-272): "-1" is
+ * refused, "40000" stored as -25536; f and B:f = float32(ParseFloat(s, 32)): [+-]digits[.digits][(e|E)[+-]digits] with a digit in the
+ * mantissa, [+-]inf / infinity, unsigned nan (0x7FC00000), the float32 NEAREST the decimal with ties to even, read directly and not via a
+ * double; beyond the largest float32 ELP_ERR_DATA, underflow +-0.  A tab behind the last field ends the line, as in the reference.
+ * strconv is restated from its documentation (csrc/samparse.hpp): no Go toolchain was at hand to run against.
+ *   ELP_ERR_DATA: what the reference panics on - the above, an empty CIGAR length, an unknown operation, a length beyond int32, an
+ * unknown field type, a field that is not KK:T:, "B:c" without comma or entry, a number that does not parse.  ELP_ERR_UNSUPPORTED: what
+ * the reference reads and this call does not - an RNAME / RNEXT that is neither "*" / "=" nor in the dictionary (the reference's BAM
+ * writer makes -1 of it, its SAM writer keeps the string, which the emitters here cannot print); a merged CIGAR length above 2^28 - 1,
+ * more than 65535 operations; len(QUAL) != len(SEQ) (the reference writes a record whose l_seq and QUAL disagree); QNAME above 254 bytes
+ * or with a NUL; two fields of one key in a line (SmallMap.Set would overwrite the first in place); an i value outside
+ * [-2^31, 2^32 - 1]; a NUL in a Z value; H fields (as the emitters); hexadecimal floats, underscores in floats, float tokens above 64
+ * bytes; more than 245 optional fields in a line; a tab as a key byte or as the value of an A field (the reference's scanner steps over
+ * it; here the line is ELP_ERR_DATA).
+ *   Errors: the first bad line of a piece decides; elp_last_error names its 0-based line number within the call and the reason.  Errors
+ * are found in the size pass, before anything of the piece is committed: a text of up to 256 MiB is one piece and is staged whole or not
+ * at all; of a longer text the pieces in front of the refused one stay staged, as elp_stage_bam leaves them (elp_num_records tells).
+ * elp_set_tuning("sam_pass") caps the lines per write pass (tests).
+ * Reads: the header, read-group ids, names.  Writes: what elp_stage_bam writes; invalidates what it invalidates. */
+int elp_stage_sam(elp_ctx *ctx, const uint8_t *text, uint64_t n_bytes, uint16_t split_id);
 /* The merge of `elprep merge` / `sfm` phase 3 with payloads (MergeSortedFilesSplitPerChromosome, sam/split-merge.go:410-576): the sorted
  * outputs of a context that holds group splits and of the context that holds the spread split as ONE stream of BAM records in the merge's
  * order (elp_merge_spread's slots), gathered in HBM.  Both contexts staged with elp_stage_bam, on one device, each coordinate-sorted

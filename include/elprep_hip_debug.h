@@ -39,6 +39,7 @@ int elp_rollback(elp_ctx *ctx);
  *   "exchange_piece"   > 0: records per piece of elp_exchange_records (default 4 M, less for long records: a piece's columns stay below 4 GiB)
  *   "bgzf_stored"      1: elp_emit_sorted_bgzf frames stored DEFLATE blocks (BTYPE 00) instead of compressing
  *   "emit_pass"        > 0: at most this many records per pass of the BAM / BGZF emitters (default 2 M, less for long records)
+ *   "sam_pass"         > 0: at most this many lines per write pass of elp_stage_sam (default: all lines of a piece of text at once)
  *   "bgzf_piece"       inflated bytes per record-scan pass of elp_stage_bgzf (default 1 GiB)
  *   "bgzf_inflate_piece"  inflated bytes whose blocks one launch of the decoder takes (default 2 GiB; the scan passes of
  *                      "bgzf_piece" bytes run inside it; token scratch: 171 KB per 64 KB block)
