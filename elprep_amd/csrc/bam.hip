@@ -145,8 +145,13 @@ __global__ __launch_bounds__(256) void k_bam_payload(BamPay m) {
 // size of output record k (block_size field included); *tags_at = offset of the tags inside the input record
 // OPT: a tag filter or a replacing read group is set.  The walks are bound by their chain of dependent loads and the per-field tests cost
 // the emitter 8 % where nothing is set (measured), so a context without either runs the instantiation without them.
-template <bool OPT>
-__device__ inline uint32_t out_size(const BamOut &m, uint32_t i, uint32_t *err) {
+// SR: the split emitters (split.hip), an instantiation of its own for the same reason; set_sr = this output record is the tagged copy of a
+// spread record and gets aln.TAGS.Set(sr, int64(1)) (sam/split-merge.go:290; SmallMap.Set, utils/small-map.go:59-67): the FIRST field with
+// key sr, whatever its type, goes out as s r C 0x01 (formatBamTag, sam/bam-files.go:509-513: 1 is type C), a record without one gets it
+// behind its last field.  elp_emit_split_* refuses a tag filter and a replacing read group, so SR never meets OPT.
+template <bool OPT, bool SR = false>
+__device__ inline uint32_t out_size(const BamOut &m, uint32_t i, uint32_t *err, bool set_sr = false) {
+  static_assert(!(OPT && SR), "the split emitters run without a tag filter and a replacing read group");
   const uint8_t *p = m.raw + m.raw_off[i];
   const uint32_t bs = ld_u32(p);
   const uint8_t *rec = p + 4, *end = rec + bs;
@@ -156,7 +161,7 @@ __device__ inline uint32_t out_size(const BamOut &m, uint32_t i, uint32_t *err) 
   const uint64_t n_cig_out = m.cigar_off[i + 1] - m.cigar_off[i];
   uint32_t size = 4 + (uint32_t)(fixed + 4ull * n_cig_out - 4ull * n_cig);
   const uint8_t *t = rec + fixed;
-  bool rg_seen = false;
+  bool rg_seen = false, sr_seen = false;
   while (t + 3 <= end) {
     const uint8_t ty = t[2];
     const uint8_t *v = t + 3;
@@ -172,6 +177,11 @@ __device__ inline uint32_t out_size(const BamOut &m, uint32_t i, uint32_t *err) 
         else size += 3 + (tag_is_int(ty) ? int_out(tag_int_value(ty, v), &ot) : sz);
       }
       rg_seen |= key == KEY_RG;
+    } else if constexpr (SR) {
+      const bool is_sr = tag_key(t) == KEY_SR;
+      if (set_sr && is_sr && !sr_seen) size += 4;
+      else size += 3 + (tag_is_int(ty) ? int_out(tag_int_value(ty, v), &ot) : sz);
+      sr_seen |= is_sr;
     } else {
       size += 3 + (tag_is_int(ty) ? int_out(tag_int_value(ty, v), &ot) : sz);
     }
@@ -179,28 +189,32 @@ __device__ inline uint32_t out_size(const BamOut &m, uint32_t i, uint32_t *err) 
   }
   if constexpr (OPT)
     if (m.rg_on && !rg_seen && !tag_dropped(m.drop, KEY_RG)) size += 4 + m.rg_len;  // ... else appended behind the last field
+  if constexpr (SR)
+    if (set_sr && !sr_seen) size += 4;
   return size;
 }
-template <bool OPT>
+template <bool OPT, bool SR = false>
 __global__ __launch_bounds__(256) void k_bam_out_sizes(BamOut m, BamOut m2, const uint32_t *__restrict__ src, uint64_t k0, uint32_t cnt, uint32_t *__restrict__ sizes,
                                                        uint32_t *err) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= cnt) return;
   uint32_t e = 0, i;
-  const BamOut &mm = out_source(m, m2, src, k0 + j, &i);
-  sizes[j] = out_size<OPT>(mm, i, &e);
+  bool set_sr;
+  const BamOut &mm = out_source<SR>(m, m2, src, k0 + j, &i, &set_sr);
+  sizes[j] = out_size<OPT, SR>(mm, i, &e, set_sr);
   if (e) atomicOr(err, e);
 }
 // (Alignment.bin(): reg2bin / record_bin, bamout.hpp)
 // one wavefront per output record; `out` = this chunk's buffer, offs = exclusive scan of the chunk's sizes
-template <bool OPT>
+template <bool OPT, bool SR = false>
 __global__ __launch_bounds__(256) void k_bam_out_emit(BamOut m_first, BamOut m_second, const uint32_t *__restrict__ src, uint64_t k0, uint32_t cnt,
                                                       const uint32_t *__restrict__ offs, uint8_t *__restrict__ out) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
   for (uint32_t j = wave; j < cnt; j += nwaves) {
     uint32_t i;
-    const BamOut &m = out_source(m_first, m_second, src, k0 + j, &i);
+    bool set_sr;  // (wave-uniform, as i)
+    const BamOut &m = out_source<SR>(m_first, m_second, src, k0 + j, &i, &set_sr);
     const uint8_t *p = m.raw + m.raw_off[i];
     const uint32_t bs = ld_u32(p);
     const uint8_t *rec = p + 4, *end = rec + bs;
@@ -239,7 +253,8 @@ __global__ __launch_bounds__(256) void k_bam_out_emit(BamOut m_first, BamOut m_s
       const uint8_t *t = rec + (32ull + l_name + 4ull * ld_u16(rec + 12) + ((ld_u32(rec + 16) + 1) >> 1) + ld_u32(rec + 16));
       // elp_set_tag_filter / elp_set_replace_read_group: the same walk - a dropped field is skipped by the whole wave together (the key
       // and the table's word are wave-uniform), the first RG field goes out as RG:Z:<id>, a record without one gets it behind its last field
-      bool rg_seen = false;
+      // elp_emit_split_* (SR): the tagged copy's first sr field goes out as sr:C:1 the same way, a copy without one gets it behind its last field
+      bool rg_seen = false, sr_seen = false;
       while (t + 3 <= end) {
         const uint8_t ty = t[2];
         const uint8_t *v = t + 3;
@@ -257,18 +272,26 @@ __global__ __launch_bounds__(256) void k_bam_out_emit(BamOut m_first, BamOut m_s
           sz = tag_value_size(ty, v, end);
         }
         if (!sz) break;
-        bool dropped = false, is_rg = false;
+        bool dropped = false, is_rg = false, is_sr = false;
         if constexpr (OPT) {
           const uint32_t key = tag_key(t);
           dropped = tag_dropped(m.drop, key);
           is_rg = m.rg_on && key == KEY_RG && !rg_seen;
           rg_seen |= key == KEY_RG;
         }
+        if constexpr (SR) {
+          const bool key_sr = tag_key(t) == KEY_SR;
+          is_sr = set_sr && key_sr && !sr_seen;
+          sr_seen |= key_sr;
+        }
         if (dropped) {
         } else if (is_rg) {
           if (lane == 0) { w[0] = 'R'; w[1] = 'G'; w[2] = 'Z'; w[3 + m.rg_len] = 0; }
           for (uint32_t b = lane; b < m.rg_len; b += 64) w[3 + b] = m.rg_new[b];
           w += 4 + m.rg_len;
+        } else if (SR && is_sr) {
+          if (lane == 0) { w[0] = 's'; w[1] = 'r'; w[2] = 'C'; w[3] = 1; }
+          w += 4;
         } else if (tag_is_int(ty)) {
           const long long val = tag_int_value(ty, v);
           uint8_t ot;
@@ -288,6 +311,10 @@ __global__ __launch_bounds__(256) void k_bam_out_emit(BamOut m_first, BamOut m_s
         if (lane == 0) { w[0] = 'R'; w[1] = 'G'; w[2] = 'Z'; w[3 + m.rg_len] = 0; }
         for (uint32_t b = lane; b < m.rg_len; b += 64) w[3 + b] = m.rg_new[b];
         w += 4 + m.rg_len;
+      }
+      if (SR && set_sr && !sr_seen) {
+        if (lane == 0) { w[0] = 's'; w[1] = 'r'; w[2] = 'C'; w[3] = 1; }
+        w += 4;
       }
       if (lane == 0) st_u32(o, (uint32_t)(w - o - 4));  // block_size
     }
@@ -540,9 +567,11 @@ int elp_stage_bam(elp_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint
 // the chunked size / scan / gather loop of both emit calls; src (device, n_out entries) or nullptr
 // fmt: the format of the stream - BAM records as they are; BGZF: the same as BGZF blocks (bgzf.hip), framed on the device pass by pass;
 // SAM: lines (sam.hip's kernels, with the names `nm`, which the other formats do not read).  who: the entry point, for error messages
-enum class OutFormat { BAM, BGZF, SAM };
-static int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint32_t *src, uint64_t n_out, uint64_t max_raw_rec, uint8_t *out, uint64_t cap,
-                       uint64_t *n_bytes_out, OutFormat fmt, const SamNames &nm, const char *who) {
+// (declared in bamout.hpp: split.hip runs it once per split file, on that file's slice of its list - m.sr_on)
+}  // extern "C"
+namespace elp {
+int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint32_t *src, uint64_t n_out, uint64_t max_raw_rec, uint8_t *out, uint64_t cap,
+                uint64_t *n_bytes_out, OutFormat fmt, const SamNames &nm, const char *who) {
   const bool bgzf = fmt == OutFormat::BGZF, sam = fmt == OutFormat::SAM;
   // records per device pass: sizes and offsets of a pass are scanned in 32 bits, so a pass must stay below 4 GiB of output.  An output
   // record is never longer than the staged one (integer fields only shrink when re-encoded) - except that elp_clean_sam may have added
@@ -575,7 +604,9 @@ static int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint
     uint32_t *offs = sizes + cnt + 8, *err = offs + cnt + 8;
     ELP_HIP(c, hipMemsetAsync(err, 0, 4, st));
     const bool opt = m.drop != nullptr || m.rg_on;  // (m2 shares m's settings: elp_emit_merged_bam checks)
+    const bool sr = m.sr_on != 0;                   // (the split emitters: never with `opt`, elp_emit_split_* refuses)
     if (sam) ELP_TRY(sam_sizes_launch(c, m, m2, nm, src, k0, cnt, sizes, err));
+    else if (sr) ELP_LAUNCH(c, "emit_split_bam_sizes", (k_bam_out_sizes<false, true>), dim3(blocks_for(cnt, 256)), dim3(256), 0, m, m2, src, k0, cnt, sizes, err);
     else if (opt) ELP_LAUNCH(c, "emit_bam_sizes", k_bam_out_sizes<true>, dim3(blocks_for(cnt, 256)), dim3(256), 0, m, m2, src, k0, cnt, sizes, err);
     else ELP_LAUNCH(c, "emit_bam_sizes", k_bam_out_sizes<false>, dim3(blocks_for(cnt, 256)), dim3(256), 0, m, m2, src, k0, cnt, sizes, err);
     uint32_t chunk_bytes = 0;
@@ -599,6 +630,7 @@ static int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint
     if (held) ELP_HIP(c, hipMemcpyAsync(d_out, carry.data(), held, hipMemcpyHostToDevice, st));
     const unsigned grid = std::min<unsigned>(blocks_for((uint64_t)cnt * 64, 256), (unsigned)c->n_cu * 32);
     if (sam) ELP_TRY(sam_emit_launch(c, m, m2, nm, src, k0, cnt, offs, d_out));
+    else if (sr) ELP_LAUNCH(c, "emit_split_bam", (k_bam_out_emit<false, true>), dim3(grid), dim3(256), 0, m, m2, src, k0, cnt, (const uint32_t *)offs, d_out + held);
     else if (opt) ELP_LAUNCH(c, "emit_bam", k_bam_out_emit<true>, dim3(grid), dim3(256), 0, m, m2, src, k0, cnt, (const uint32_t *)offs, d_out + held);
     else ELP_LAUNCH(c, "emit_bam", k_bam_out_emit<false>, dim3(grid), dim3(256), 0, m, m2, src, k0, cnt, (const uint32_t *)offs, d_out + held);
     const uint8_t *d_send = d_out;
@@ -621,11 +653,22 @@ static int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint
   *n_bytes_out = total;
   return 0;
 }
-static BamOut bam_out_of(const elp_ctx *c) {
+BamOut bam_out_of(const elp_ctx *c) {
   return BamOut{c->n - c->n_sr, c->perm.p, c->raw.p, c->raw_off.p, c->refid.p, c->pos.p, c->next_refid.p, c->pnext.p, c->tlen.p, c->flag.p, c->mapq.p, c->l_seq.p,
                 c->qname_off.p, c->cigar_off.p, c->qual_off.p, c->qname.p, c->qual.p, c->cigar.p, c->tag_filter ? c->tag_drop.p : nullptr,
-                c->replace_rg_dev.p, c->replace_rg ? (uint32_t)c->replace_rg_id.size() : 0u, c->replace_rg ? 1u : 0u};
+                c->replace_rg_dev.p, c->replace_rg ? (uint32_t)c->replace_rg_id.size() : 0u, c->replace_rg ? 1u : 0u, 0u};
 }
+SamNames sam_names_of(const elp_ctx *c) { return SamNames{c->ref_names.p, c->ref_names_off.p, c->n_ref, c->max_ref_name}; }
+// what the SAM emitters ask beyond their BAM counterparts: the names of the dictionary in force, in a stream of two contexts equal ones
+int sam_names_checks(elp_ctx *c, elp_ctx *other, const char *who) {
+  if (!c->have_ref_names || (other && !other->have_ref_names))
+    return set_error(c, ELP_ERR_ARG, "%s: the reference names are not set (elp_set_reference_names_flat, for the dictionary the context holds now)", who);
+  if (other && (c->h_ref_names != other->h_ref_names || c->h_ref_names_off != other->h_ref_names_off))
+    return set_error(c, ELP_ERR_ARG, "%s: the two contexts' reference names differ (elp_set_reference_names_flat)", who);
+  return 0;
+}
+}  // namespace elp
+extern "C" {
 // the largest output record is bounded by the largest staged one + this (emit_stream adds the CIGAR operation of elp_clean_sam)
 static uint64_t out_growth(const elp_ctx *c) { return c->replace_rg ? 4 + (uint64_t)c->replace_rg_id.size() : 0; }
 
@@ -677,15 +720,6 @@ static int two_context_checks(elp_ctx *groups, elp_ctx *spread, const char *who)
   if (!same_replace_rg(groups, spread)) return set_error(groups, ELP_ERR_ARG, "%s: the two contexts' replacing read groups differ (elp_set_replace_read_group)", who);
   if (groups->dict_replaced != spread->dict_replaced)
     return set_error(groups, ELP_ERR_ARG, "%s: one context has replaced its reference dictionary, the other has not (elp_replace_reference_dictionary)", who);
-  return 0;
-}
-static SamNames sam_names_of(const elp_ctx *c) { return SamNames{c->ref_names.p, c->ref_names_off.p, c->n_ref, c->max_ref_name}; }
-// what the SAM emitters ask beyond their BAM counterparts: the names of the dictionary in force, in a stream of two contexts equal ones
-static int sam_names_checks(elp_ctx *c, elp_ctx *other, const char *who) {
-  if (!c->have_ref_names || (other && !other->have_ref_names))
-    return set_error(c, ELP_ERR_ARG, "%s: the reference names are not set (elp_set_reference_names_flat, for the dictionary the context holds now)", who);
-  if (other && (c->h_ref_names != other->h_ref_names || c->h_ref_names_off != other->h_ref_names_off))
-    return set_error(c, ELP_ERR_ARG, "%s: the two contexts' reference names differ (elp_set_reference_names_flat)", who);
   return 0;
 }
 static int emit_two(elp_ctx *groups, elp_ctx *spread, const uint32_t *src, uint64_t n_out, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out, OutFormat fmt,

@@ -23,8 +23,10 @@ struct BamOut {
   const uint32_t *drop;      // elp_set_tag_filter: bit k = fields with the 16-bit key k stay behind (65536 bits); nullptr = no filter
   const uint8_t *rg_new;     // elp_set_replace_read_group: the id every record goes out with (rg_on), rg_len bytes
   uint32_t rg_len, rg_on;
+  uint32_t sr_on;            // the split emitters (split.hip): src is their emission list - staging indices, bit 31 = the tagged copy
 };
 constexpr uint32_t KEY_RG = tag_key_of('R', 'G');
+constexpr uint32_t KEY_SR = tag_key_of('s', 'r');
 // filters2's RemoveOptionalFields / KeepOptionalFields (filters/simple-filters.go:235-288) as one look-up: every field of a key goes or stays
 __device__ __forceinline__ bool tag_dropped(const uint32_t *__restrict__ drop, uint32_t key) { return drop && ((drop[key >> 5] >> (key & 31)) & 1u); }
 // Output record k of a MERGED stream (elp_emit_merged_bam) comes from one of two contexts: src[k] = rank of the record in the first
@@ -35,6 +37,22 @@ __device__ __forceinline__ const BamOut &out_source(const BamOut &m, const BamOu
   const BamOut &mm = (s & MERGE_SECOND) ? m2 : m;
   *i = mm.perm[s & ~MERGE_SECOND];
   return mm;
+}
+// The split emitters' list (elp_emit_split_*, split.hip) names records by STAGING index, not by rank in a permutation; bit 31 of an entry
+// marks the copy that stays in the group file of a record that also goes to the spread file: it gets aln.TAGS.Set(sr, int64(1))
+// (sam/split-merge.go:290).  SR = false is out_source as it is.
+constexpr uint32_t SPLIT_TAGGED = 0x80000000u;
+template <bool SR>
+__device__ __forceinline__ const BamOut &out_source(const BamOut &m, const BamOut &m2, const uint32_t *__restrict__ src, uint64_t k, uint32_t *i, bool *set_sr) {
+  if constexpr (SR) {
+    const uint32_t s = src[k];
+    *i = s & ~SPLIT_TAGGED;
+    *set_sr = (s & SPLIT_TAGGED) != 0;
+    return m;
+  } else {
+    *set_sr = false;
+    return out_source(m, m2, src, k, i);
+  }
 }
 
 // Alignment.bin(), sam/bam-files.go:443-468
@@ -65,5 +83,14 @@ struct SamNames {
 // BAM kernels take them)
 int sam_sizes_launch(elp_ctx *c, const BamOut &m, const BamOut &m2, const SamNames &nm, const uint32_t *src, uint64_t k0, uint32_t cnt, uint32_t *sizes, uint32_t *err);
 int sam_emit_launch(elp_ctx *c, const BamOut &m, const BamOut &m2, const SamNames &nm, const uint32_t *src, uint64_t k0, uint32_t cnt, const uint32_t *offs, uint8_t *out);
+
+// bam.hip, for the emitters of other files (split.hip): the chunked size / scan / gather loop over n_out output records, the context's
+// columns as the kernels take them, its reference names and the check that they are set
+enum class OutFormat { BAM, BGZF, SAM };
+int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint32_t *src, uint64_t n_out, uint64_t max_raw_rec, uint8_t *out, uint64_t cap,
+                uint64_t *n_bytes_out, OutFormat fmt, const SamNames &nm, const char *who);
+BamOut bam_out_of(const elp_ctx *c);
+SamNames sam_names_of(const elp_ctx *c);
+int sam_names_checks(elp_ctx *c, elp_ctx *other, const char *who);
 
 }  // namespace elp

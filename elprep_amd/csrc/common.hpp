@@ -477,6 +477,16 @@ __host__ __device__ inline uint16_t mod_flag(uint16_t flag) {
   return flag;
 }
 
+// SplitFilePerChromosome's routing rule (sam/split-merge.go:280-293) for a record with these refids: *g = its split file - 0 for RNAME "*"
+// (contigToGroup["*"] = "unmapped", :254), else group_of_ref[refid] -; returns whether it also goes to the spread file (:286: RNEXT != "=",
+// which in BAM is next_refid != refid (sam/bam-files.go:344-346), RNAME != "*", and the mate's group differs - so a mapped record with RNEXT
+// "*" is spread).  elp_split_classify (filter.hip) and the split emitters' list (split.hip) route by it.
+__device__ __forceinline__ bool split_route(int32_t r, int32_t nr, const int32_t *__restrict__ group_of_ref, int32_t n_ref, int32_t *g) {
+  *g = (r >= 0 && r < n_ref) ? group_of_ref[r] : 0;
+  const int32_t gn = (nr >= 0 && nr < n_ref) ? group_of_ref[nr] : 0;
+  return nr != r && r >= 0 && gn != *g;
+}
+
 // ---- cross-TU entry points ----
 int radix_sort_pairs(elp_ctx *c, uint64_t *keys, uint32_t *vals, uint64_t *keys_tmp, uint32_t *vals_tmp, uint64_t n,
                      uint64_t **keys_out, uint32_t **vals_out);

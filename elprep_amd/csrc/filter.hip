@@ -222,11 +222,8 @@ __global__ __launch_bounds__(256) void k_split_classify(uint64_t n, const int32_
   for (int k = threadIdx.x; k < n_groups + 2; k += blockDim.x) lds_cnt[k] = 0;
   __syncthreads();
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const int32_t r = refid[i], nr = next_refid[i];
-    const int32_t g = (r >= 0 && r < n_ref) ? group_of_ref[r] : 0;       // contigToGroup["*"] = "unmapped" (:254)
-    const int32_t gn = (nr >= 0 && nr < n_ref) ? group_of_ref[nr] : 0;
-    // :286: RNEXT != "=" (BAM: next_refid != refid, sam/bam-files.go:344-346), RNAME != "*", and the mate's group differs
-    const bool spread = nr != r && r >= 0 && gn != g;
+    int32_t g;
+    const bool spread = split_route(refid[i], next_refid[i], group_of_ref, n_ref, &g);  // (common.hpp: the rule the split emitters share)
     split_out[i] = (uint16_t)g;
     split_col[i] = (uint16_t)g;  // the record's split file: travels with it (elp_copy_records / elp_exchange_records keep it)
     spread_out[i] = spread ? 1 : 0;

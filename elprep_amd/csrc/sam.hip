@@ -24,9 +24,13 @@ namespace elp {
 
 namespace st = samtext;
 
+constexpr uint32_t SR_TEXT_LEN = 7;  // "\tsr:i:1"
 // text size of output record k; the error bits of the BAM size pass (2 malformed fields, 16 an H field) and 32: a refid outside the names
-template <bool OPT>
-__device__ inline uint32_t sam_out_size(const BamOut &m, const SamNames &nm, uint32_t i, uint32_t *err) {
+// SR (the split emitters, split.hip), set_sr: as out_size's (bam.hip) - the tagged copy's first sr field goes out as "\tsr:i:1", a copy
+// without one gets it behind its last field
+template <bool OPT, bool SR = false>
+__device__ inline uint32_t sam_out_size(const BamOut &m, const SamNames &nm, uint32_t i, uint32_t *err, bool set_sr = false) {
+  static_assert(!(OPT && SR), "the split emitters run without a tag filter and a replacing read group");
   const uint8_t *p = m.raw + m.raw_off[i];
   const uint32_t bs = ld_u32(p);
   const uint8_t *rec = p + 4, *end = rec + bs;
@@ -46,7 +50,7 @@ __device__ inline uint32_t sam_out_size(const BamOut &m, const SamNames &nm, uin
   size += 2u * m.l_seq[i];  // (the column, as the emit pass reads it; equal to the staged field)
   // the optional fields: out_size's walk (bam.hip), counting text
   const uint8_t *t = rec + fixed;
-  bool rg_seen = false;
+  bool rg_seen = false, sr_seen = false;
   while (t + 3 <= end) {
     const uint8_t ty = t[2];
     const uint8_t *v = t + 3;
@@ -60,6 +64,11 @@ __device__ inline uint32_t sam_out_size(const BamOut &m, const SamNames &nm, uin
         else size += st::put_field(nullptr, t, ty, v, sz);
       }
       rg_seen |= key == KEY_RG;
+    } else if constexpr (SR) {
+      const bool is_sr = tag_key(t) == KEY_SR;
+      if (set_sr && is_sr && !sr_seen) size += SR_TEXT_LEN;
+      else size += st::put_field(nullptr, t, ty, v, sz);
+      sr_seen |= is_sr;
     } else {
       size += st::put_field(nullptr, t, ty, v, sz);
     }
@@ -67,16 +76,19 @@ __device__ inline uint32_t sam_out_size(const BamOut &m, const SamNames &nm, uin
   }
   if constexpr (OPT)
     if (m.rg_on && !rg_seen && !tag_dropped(m.drop, KEY_RG)) size += 6 + m.rg_len;
+  if constexpr (SR)
+    if (set_sr && !sr_seen) size += SR_TEXT_LEN;
   return size;
 }
-template <bool OPT>
+template <bool OPT, bool SR = false>
 __global__ __launch_bounds__(256) void k_sam_out_sizes(BamOut m, BamOut m2, SamNames nm, const uint32_t *__restrict__ src, uint64_t k0, uint32_t cnt,
                                                        uint32_t *__restrict__ sizes, uint32_t *err) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= cnt) return;
   uint32_t e = 0, i;
-  const BamOut &mm = out_source(m, m2, src, k0 + j, &i);
-  sizes[j] = sam_out_size<OPT>(mm, nm, i, &e);
+  bool set_sr;
+  const BamOut &mm = out_source<SR>(m, m2, src, k0 + j, &i, &set_sr);
+  sizes[j] = sam_out_size<OPT, SR>(mm, nm, i, &e, set_sr);
   if (e) atomicOr(err, e);
 }
 
@@ -105,19 +117,24 @@ __device__ __forceinline__ uint32_t put_rg(uint8_t *w, const BamOut &m, uint32_t
   for (uint32_t b = lane; b < m.rg_len; b += 64) w[6 + b] = m.rg_new[b];
   return 6 + m.rg_len;
 }
+__device__ __forceinline__ uint32_t put_sr(uint8_t *w, uint32_t lane) {
+  if (lane == 0) { w[0] = '\t'; w[1] = 's'; w[2] = 'r'; w[3] = ':'; w[4] = 'i'; w[5] = ':'; w[6] = '1'; }
+  return SR_TEXT_LEN;
+}
 
 // one wavefront per output line; `out` = this chunk's buffer, offs = exclusive scan of the chunk's sizes.  The lanes copy QNAME, the names,
 // SEQ (a lane takes one staged byte: two bases), QUAL and Z values in strides of 64; the few numbers of the fixed columns and of scalar
 // fields are lane 0's, which tells the wave how far it wrote.  CIGAR operations and B elements have texts of different widths: every
 // lane formats one, a prefix sum over the wave places them, the running offset carries over the steps of 64.
-template <bool OPT>
+template <bool OPT, bool SR = false>
 __global__ __launch_bounds__(256) void k_sam_out_emit(BamOut m_first, BamOut m_second, SamNames nm, const uint32_t *__restrict__ src, uint64_t k0, uint32_t cnt,
                                                       const uint32_t *__restrict__ offs, uint8_t *__restrict__ out) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
   for (uint32_t j = wave; j < cnt; j += nwaves) {
     uint32_t i;
-    const BamOut &m = out_source(m_first, m_second, src, k0 + j, &i);
+    bool set_sr;  // (wave-uniform, as i)
+    const BamOut &m = out_source<SR>(m_first, m_second, src, k0 + j, &i, &set_sr);
     const uint8_t *p = m.raw + m.raw_off[i];
     const uint32_t bs = ld_u32(p);
     const uint8_t *rec = p + 4, *end = rec + bs;
@@ -186,7 +203,7 @@ __global__ __launch_bounds__(256) void k_sam_out_emit(BamOut m_first, BamOut m_s
     w += l_seq;
     // the optional fields: the BAM emitter's wave-uniform walk (k_bam_out_emit), writing text
     const uint8_t *t = rec + (32ull + l_name + 4ull * ld_u16(rec + 12) + ((ld_u32(rec + 16) + 1) >> 1) + ld_u32(rec + 16));
-    bool rg_seen = false;
+    bool rg_seen = false, sr_seen = false;
     while (t + 3 <= end) {
       const uint8_t ty = t[2];
       const uint8_t *v = t + 3;
@@ -204,16 +221,23 @@ __global__ __launch_bounds__(256) void k_sam_out_emit(BamOut m_first, BamOut m_s
         sz = tag_value_size(ty, v, end);
       }
       if (!sz) break;
-      bool dropped = false, is_rg = false;
+      bool dropped = false, is_rg = false, is_sr = false;
       if constexpr (OPT) {
         const uint32_t key = tag_key(t);
         dropped = tag_dropped(m.drop, key);
         is_rg = m.rg_on && key == KEY_RG && !rg_seen;
         rg_seen |= key == KEY_RG;
       }
+      if constexpr (SR) {
+        const bool key_sr = tag_key(t) == KEY_SR;
+        is_sr = set_sr && key_sr && !sr_seen;
+        sr_seen |= key_sr;
+      }
       if (dropped) {
       } else if (is_rg) {
         w += put_rg(w, m, lane);
+      } else if (SR && is_sr) {
+        w += put_sr(w, lane);
       } else if (ty == 'Z' || ty == 'H') {
         if (lane == 0) { w[0] = '\t'; w[1] = t[0]; w[2] = t[1]; w[3] = ':'; w[4] = ty; w[5] = ':'; }
         for (uint32_t b = lane; b + 1 < sz; b += 64) w[6 + b] = v[b];
@@ -244,20 +268,23 @@ __global__ __launch_bounds__(256) void k_sam_out_emit(BamOut m_first, BamOut m_s
       t = v + sz;
     }
     if (OPT && m.rg_on && !rg_seen && !tag_dropped(m.drop, KEY_RG)) w += put_rg(w, m, lane);
+    if (SR && set_sr && !sr_seen) w += put_sr(w, lane);
     if (lane == 0) w[0] = '\n';
   }
 }
 
 int sam_sizes_launch(elp_ctx *c, const BamOut &m, const BamOut &m2, const SamNames &nm, const uint32_t *src, uint64_t k0, uint32_t cnt, uint32_t *sizes, uint32_t *err) {
   const bool opt = m.drop != nullptr || m.rg_on;  // (m2 shares m's settings, as in the BAM emitters)
-  if (opt) ELP_LAUNCH(c, "emit_sam_sizes", k_sam_out_sizes<true>, dim3(blocks_for(cnt, 256)), dim3(256), 0, m, m2, nm, src, k0, cnt, sizes, err);
+  if (m.sr_on) ELP_LAUNCH(c, "emit_split_sam_sizes", (k_sam_out_sizes<false, true>), dim3(blocks_for(cnt, 256)), dim3(256), 0, m, m2, nm, src, k0, cnt, sizes, err);
+  else if (opt) ELP_LAUNCH(c, "emit_sam_sizes", k_sam_out_sizes<true>, dim3(blocks_for(cnt, 256)), dim3(256), 0, m, m2, nm, src, k0, cnt, sizes, err);
   else ELP_LAUNCH(c, "emit_sam_sizes", k_sam_out_sizes<false>, dim3(blocks_for(cnt, 256)), dim3(256), 0, m, m2, nm, src, k0, cnt, sizes, err);
   return 0;
 }
 int sam_emit_launch(elp_ctx *c, const BamOut &m, const BamOut &m2, const SamNames &nm, const uint32_t *src, uint64_t k0, uint32_t cnt, const uint32_t *offs, uint8_t *out) {
   const bool opt = m.drop != nullptr || m.rg_on;
   const unsigned grid = std::min<unsigned>(blocks_for((uint64_t)cnt * 64, 256), (unsigned)c->n_cu * 32);
-  if (opt) ELP_LAUNCH(c, "emit_sam", k_sam_out_emit<true>, dim3(grid), dim3(256), 0, m, m2, nm, src, k0, cnt, offs, out);
+  if (m.sr_on) ELP_LAUNCH(c, "emit_split_sam", (k_sam_out_emit<false, true>), dim3(grid), dim3(256), 0, m, m2, nm, src, k0, cnt, offs, out);
+  else if (opt) ELP_LAUNCH(c, "emit_sam", k_sam_out_emit<true>, dim3(grid), dim3(256), 0, m, m2, nm, src, k0, cnt, offs, out);
   else ELP_LAUNCH(c, "emit_sam", k_sam_out_emit<false>, dim3(grid), dim3(256), 0, m, m2, nm, src, k0, cnt, offs, out);
   return 0;
 }

@@ -14,7 +14,7 @@
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -421,6 +421,25 @@ class Engine:
         counts = np.zeros(n_groups + 2, dtype=np.uint64)
         self._check(self.L.elp_split_classify(self.h, _vp(g), n_groups, _vp(split), _vp(spread), _vp(counts)))
         return split, spread, counts
+
+    def emit_split(self, group_of_ref: np.ndarray, n_groups: int, fmt: str = "bam", single_end: bool = False) -> List[np.ndarray]:
+        """the files of `elprep split` of the staged records (elp_emit_split_bam / _bgzf / _sam; fmt = "bam", "bgzf" or "sam"): one uint8
+        array per file - the unmapped file, the group files 1 .. n_groups and, unless single_end, the spread file - without header text or
+        blocks and without the BGZF end-of-file block.  A group file holds the copies of its spread records with sr:i:1 set"""
+        fn = {"bam": self.L.elp_emit_split_bam, "bgzf": self.L.elp_emit_split_bgzf, "sam": self.L.elp_emit_split_sam}[fmt]
+        if fmt == "sam":
+            self._header_names()
+        g = np.ascontiguousarray(group_of_ref, dtype=np.int32)
+        if g.size != self._n_ref_in_force():  # (the library reads group_of_ref[0 .. n_ref) of the dictionary in force)
+            raise ElpError(-1, "emit_split: group_of_ref has %d entries, the context's dictionary %d contigs" % (g.size, self._n_ref_in_force()))
+        if g.size == 0:
+            g = np.zeros(1, np.int32)  # (a dictionary without contigs: the pointer must not be NULL)
+        off = np.zeros(max(int(n_groups), 0) + (2 if single_end else 3), dtype=np.uint64)
+        n = C.c_uint64()
+        self._check(fn(self.h, _vp(g), int(n_groups), int(bool(single_end)), C.c_void_p(0), 0, _vp(off), C.byref(n)))
+        out = np.empty(int(n.value), dtype=np.uint8)
+        self._check(fn(self.h, _vp(g), int(n_groups), int(bool(single_end)), _vp(out), out.size, _vp(off), C.byref(n)))
+        return [out[int(off[f]):int(off[f + 1])] for f in range(off.size - 1)]
 
     def merge_spread(self, spread: "Engine") -> np.ndarray:
         slots = np.empty(spread.n_sorted, dtype=np.uint64)

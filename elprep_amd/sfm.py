@@ -269,6 +269,16 @@ def route_device(reader, b: Batch, group_of_ref: np.ndarray, n_groups: int, owne
     return dst_local.n - n0, dst_spread.n - n1
 
 
+def split_files_device(reader, group_of_ref: np.ndarray, n_groups: int, fmt: str = "bam", single_end: bool = False) -> List[np.ndarray]:
+    """The file-writing counterpart of route_device: the records the READER context holds (staged from BAM or SAM bytes) leave as the
+    bytes of `elprep split`'s files (SplitFilePerChromosome / SplitSingleEndFilePerChromosome, sam/split-merge.go:225-311, 664-724) -
+    elp_emit_split_bam / _bgzf / _sam, fmt = "bam", "bgzf" or "sam".  -> one uint8 array per file: the unmapped file, the group files
+    1 .. n_groups and, unless single_end, the spread file; a group file holds the copies of its spread records with sr:i:1 set, in input
+    order among the others.  The host writes each file as header text or blocks (with the @sr co: line and the file's @cs lines), these
+    bytes, and for BGZF the end-of-file block; no payload passes through it re-encoded."""
+    return reader.emit_split(group_of_ref, n_groups, fmt=fmt, single_end=single_end)
+
+
 def _order_call(e, order: str):
     """the call that makes a context's permutation: order = "coordinate" (elp_sort_coordinate) or "keep" (elp_order_keep: the input is sorted
     already, effectiveSortingOrder turned the request into Keep, sam/filter-pipeline.go:208-225)"""

@@ -387,6 +387,42 @@ int elp_split_classify(elp_ctx *ctx, const int32_t *group_of_ref, int32_t n_grou
  *   (elp_stage_bam).  Large sets move in pieces inside the call; on an error the pieces already appended stay (elp_num_records tells). */
 int elp_copy_records(elp_ctx *dst, elp_ctx *src, const uint32_t *idx, uint64_t n, int new_split, int tag_sr);
 int elp_merge_spread(elp_ctx *groups, elp_ctx *spread, uint64_t *slot_of_spread_out);
+/* elp_emit_split_bam / _bgzf / _sam: the FILES of `elprep split`, written on the device - SplitFilePerChromosome (:225-311) and
+ *   SplitSingleEndFilePerChromosome (:664-724) with payloads.  One call writes all split files of the context's staged records behind each
+ *   other into `out`: file_off_out[f] .. file_off_out[f + 1] are the bytes of file f (n_files + 1 offsets), *n_bytes_out their total.
+ *   single_end == 0: n_files = n_groups + 2 - file 0 the unmapped file, files 1 .. n_groups the group files, file n_groups + 1 the spread
+ *   file.  single_end != 0: n_files = n_groups + 1, no spread file, nothing tagged.  group_of_ref as elp_split_classify takes it (n_ref
+ *   entries, each 0 .. n_groups); the routing is that call's rule (:280-293): a record goes to the file of its contig group, RNAME "*" to
+ *   file 0; it is spread iff next_refid != refid, refid >= 0 and the mate's group differs (so a mapped record with RNEXT "*" is spread).
+ *   Every file holds its records in staging order: a group file the untagged records and the tagged copies of the spread records among
+ *   each other, each at its record's place; the spread file the untagged originals.  Records rejected by elp_filter_records and its kin
+ *   (state 2) appear nowhere; records staged WITH an sr field (state 1: a split file that is split again) are routed and written as any
+ *   other and keep their sr fields.
+ *   A record's bytes are what the emitter of the same format writes for it (elp_emit_sorted_bam / _sam: CIGAR from the CIGAR column, FLAG
+ *   and QUAL as they are now, integers re-encoded in their smallest type).  A tagged copy additionally gets aln.TAGS.Set(sr, int64(1))
+ *   (:290; SmallMap.Set, utils/small-map.go:59-67): the FIRST field with key sr, whatever its type, goes out in its place as s r C 0x01
+ *   (SAM: sr:i:1), later sr fields stay as they are, a record without one gets the field behind its last field (4 bytes, SAM: "\tsr:i:1").
+ *   _bgzf: each file is framed on its own, as elp_emit_sorted_bgzf frames its stream - members of 65280 payload bytes except a file's last,
+ *   nothing carried across a file boundary, an empty file is zero bytes; inflating file f's members gives _bam's bytes of file f.
+ *   Header text or blocks - with the @sr co: line and the per-file @cs lines elprep split adds -, the BGZF end-of-file block and the file
+ *   names are the host's.  out == NULL is the size query: _bam and _sam return the exact total and offsets, _bgzf the stored form's upper
+ *   bound and bound offsets; the real call packs the files at their actual sizes.  elp_set_tuning "emit_pass" caps these passes too.
+ *   The call reads the staged records only: it needs no elp_split_classify, reads and writes neither the split-id column nor a
+ *   permutation, and invalidates nothing.
+ *   Errors: ELP_ERR_ARG for NULL arguments, n_groups < 1 or > 65533, a group_of_ref entry outside 0 .. n_groups, records that were not
+ *   staged with elp_stage_bam / _bgzf / _sam (no bytes to write), a tag filter or a replacing read group (`elprep split` has no such
+ *   options: refused, not composed), _sam without reference names, an output buffer too small (*n_bytes_out = 0);
+ *   ELP_ERR_UNSUPPORTED for more than 2^31-16 staged records (bit 31 of a list entry marks the tagged copy) and for H fields,
+ *   ELP_ERR_DATA for malformed fields, as in the other emitters.
+ *   Limits: the call is for READER contexts.  A context that received tagged copies through elp_copy_records / elp_exchange_records holds
+ *   state 1 without the field in its bytes, and such records are written without it.  MergeInputs (several input files,
+ *   sam/merge-inputs.go) stays the host's. */
+int elp_emit_split_bam(elp_ctx *ctx, const int32_t *group_of_ref, int32_t n_groups, int single_end, uint8_t *out, uint64_t cap,
+                       uint64_t *file_off_out /* n_files + 1 */, uint64_t *n_bytes_out);
+int elp_emit_split_bgzf(elp_ctx *ctx, const int32_t *group_of_ref, int32_t n_groups, int single_end, uint8_t *out, uint64_t cap,
+                        uint64_t *file_off_out /* n_files + 1 */, uint64_t *n_bytes_out);
+int elp_emit_split_sam(elp_ctx *ctx, const int32_t *group_of_ref, int32_t n_groups, int single_end, uint8_t *out, uint64_t cap,
+                       uint64_t *file_off_out /* n_files + 1 */, uint64_t *n_bytes_out);
 
 /* ---- coordinate sort: By(CoordinateLess).ParallelStableSort (sam/sam-types.go:425-473, 639-641) ----
  * Builds the permutation on device: perm[k] = staging index of the record at sorted position k; records equal
