@@ -565,7 +565,7 @@ int elp_stage_bam(elp_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint
 }
 
 // the chunked size / scan / gather loop of both emit calls; src (device, n_out entries) or nullptr
-// fmt: the format of the stream - BAM records as they are; BGZF: the same as BGZF blocks (bgzf.hip), framed on the device pass by pass;
+// fmt: the format of the stream - BAM records as they are; BGZF: the same as BGZF blocks (bgzf_out.hip), framed on the device pass by pass;
 // SAM: lines (sam.hip's kernels, with the names `nm`, which the other formats do not read).  who: the entry point, for error messages
 // (declared in bamout.hpp: split.hip runs it once per split file, on that file's slice of its list - m.sr_on)
 }  // extern "C"
@@ -593,7 +593,7 @@ int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint32_t *s
   if (c->tune.emit_pass > 0) CHUNK = std::min<uint32_t>(CHUNK, (uint32_t)c->tune.emit_pass);  // (elp_set_tuning: tests)
   uint64_t total = 0;
   hipStream_t st = c->stream;
-  // BGZF: every member but the last holds 65280 bytes of the stream (bgzf.hip's BGZF_PAYLOAD), wherever the passes fall - the bytes of a
+  // BGZF: every member but the last holds 65280 bytes of the stream (bgzf_plan.hpp's BGZF_PAYLOAD), wherever the passes fall - the bytes of a
   // pass behind its last full member are carried into the next pass and framed there (the last pass frames all it holds)
   constexpr uint64_t BGZF_MEMBER_BYTES = 65280;
   std::vector<uint8_t> carry, next_carry;
@@ -683,7 +683,7 @@ int elp_emit_sorted_bam(elp_ctx *c, uint8_t *out, uint64_t cap, uint64_t *n_byte
 }
 
 // The same records as BGZF blocks (utils/bgzf/bgzf-files.go:324-383): members of at most 65280 input bytes, COMPRESSED on the device
-// (bgzf.hip: parallel LZ77 + DEFLATE with each block's own dynamic Huffman codes, as compress/flate writes them; `elp_set_tuning`
+// (bgzf_out.hip: parallel LZ77 + DEFLATE with each block's own dynamic Huffman codes, as compress/flate writes them; `elp_set_tuning`
 // "bgzf_fixed" = 1 forces fixed codes, "bgzf_stored" = 1 stored blocks), CRC-32 and ISIZE per member, framed on the device: what follows a
 // BAM file's header blocks; the host appends the 28-byte end-of-file block (:53-62).
 // Inflating the members gives elp_emit_sorted_bam's bytes.

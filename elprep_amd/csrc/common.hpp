@@ -543,7 +543,7 @@ int install_dictionary(elp_ctx *c, int32_t n_ref, const int32_t *ref_len);
 // staging into a context whose dictionary was replaced: its columns hold new refids, the bytes to come the header's
 int staging_refused_after_replace(elp_ctx *c, const char *who);
 int stage_bam_columns(elp_ctx *c, uint32_t n_rec, uint64_t piece_bytes, uint64_t raw_end, uint64_t max_raw_rec, uint16_t split_id);  // bam.hip
-uint64_t bgzf_framed_size(uint64_t n_bytes);                                   // bgzf.hip
+uint64_t bgzf_framed_size(uint64_t n_bytes);                                   // bgzf_out.hip
 int bgzf_frame(elp_ctx *c, const uint8_t *raw, uint64_t n_bytes, uint8_t *out);  // device to device, stored blocks
 int bgzf_deflate(elp_ctx *c, const uint8_t *raw, uint64_t n_bytes, uint8_t *out, uint64_t *out_bytes);  // device to device, compressed members; *out_bytes <= bgzf_framed_size                               // BAM nibbles -> code nibbles on seq4[from, from + bytes)
 

@@ -22,7 +22,7 @@
 //   3. a scan gives every part its bit offset; every thread writes its tokens' codes at their offsets (bit-OR into the zeroed output:
 //      neighbouring parts share words).  A block whose code would not be shorter than its payload is stored (BTYPE 00).
 //
-// Everything that decides a bit is in this header as host-and-device code: the device kernel (bgzf.hip) and the host emulation the CPU
+// Everything that decides a bit is in this header as host-and-device code: the device kernel (bgzf_out.hip) and the host emulation the CPU
 // tests compile (tests/deflate_host.cpp) run the same functions in the same order of phases.
 #pragma once
 #include <cstdint>

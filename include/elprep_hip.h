@@ -145,7 +145,7 @@ int elp_emit_sorted_bam(elp_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *n_by
  * elp_stage_bgzf = the reader (:95-221) + elp_stage_bam: `bgzf` holds whole BGZF blocks of a BAM file (the file, or a part of it that
  * starts at a block and ends with a complete alignment record; an end-of-file block is skipped).  The compressed bytes are copied to the
  * device (in chunks, while the decoder works on the chunks in front), every block is inflated (RFC 1951: stored, fixed and dynamic Huffman
- * blocks; round 6, csrc/bgzf.hip: a wavefront turns the block's bit stream into literals in place and match tokens - 64 candidate symbols
+ * blocks; round 6, csrc/bgzf_inflate.hip: a wavefront turns the block's bit stream into literals in place and match tokens - 64 candidate symbols
  * per step -, a workgroup resolves the matches by pointer jumping in LDS), its CRC-32 is checked
  * ("invalid CRC-32 value for a data block in a BGZF file"), the starts of the alignment records are found on the device (every block
  * guesses its first record start, walks its records, and the guesses are proven by checking that every block's chain ends where the

@@ -1,6 +1,6 @@
 """The registers and the LDS of the BGZF kernels decide how many of their waves a CU holds - and with that their rate (round 6: a four-line
 change took the writer's kernel from 256 to 258 registers, one workgroup per CU instead of two, 22 -> 40 ms per launch; nothing failed).
-The device code of bgzf.hip is compiled to assembly (hipcc cross-compiles without a GPU) and the kernels' resource records are checked."""
+The device code of bgzf_inflate.hip and bgzf_out.hip is compiled to assembly (hipcc cross-compiles without a GPU) and the kernels' resource records are checked."""
 import os
 import re
 import shutil
@@ -32,10 +32,10 @@ def _resources(tmp_path, source):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
 def test_bgzf_kernels_keep_their_occupancy(tmp_path):
-    rec = _resources(tmp_path, "bgzf.hip")
+    rec = _resources(tmp_path, "bgzf_inflate.hip")
     tok = rec("k_bgzf_tokens")     # 24 waves per CU: <= 80 registers (six waves per SIMD), <= 6.6 KB of LDS
     assert tok["vgpr"] <= 80 and tok["lds"] <= 6600 and tok["spill"] == 0 and tok["scratch"] == 0, tok
-    dfl = rec("k_bgzf_deflate")    # two workgroups per CU: <= 256 registers, <= 80 KB of LDS
+    dfl = _resources(tmp_path, "bgzf_out.hip")("k_bgzf_deflate")    # two workgroups per CU: <= 256 registers, <= 80 KB of LDS
     assert dfl["vgpr"] <= 256 and dfl["lds"] <= 81920 and dfl["spill"] == 0 and dfl["scratch"] == 0, dfl
     res = rec("k_bgzf_resolve")    # one workgroup of 16 waves per CU: <= 128 registers; 128 KB of dynamic LDS + the CRC's tables
     assert res["vgpr"] <= 128 and res["lds"] <= 8192 and res["spill"] == 0 and res["scratch"] == 0, res
