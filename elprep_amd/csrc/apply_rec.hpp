@@ -1,5 +1,5 @@
 // apply_rec.hpp - the 8-byte per-read record of ApplyBQSR for read sets of one length (apply3.hip).  It holds nothing the LUT decides:
-// since round 6 the score kernel of the adapt stage writes it as it goes (sort.hip: k_score_uniform has the read's flags and low-quality-tail
+// since round 6 the score kernel of the adapt stage writes it as it goes (adapt.hip: k_score_uniform has the read's flags and low-quality-tail
 // bounds at hand) and k_bqsr_apply3 tests the read group's presence in the tables itself - a pass of its own over four columns
 // (k_apply_records, 0.3 ms per 50 M reads) is only made where the adapt stage ran another score kernel.
 #pragma once

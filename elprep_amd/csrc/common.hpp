@@ -504,8 +504,8 @@ int radix_sort_pairs_low(elp_ctx *c, uint64_t *keys, uint32_t *vals, uint64_t *k
                          uint64_t **keys_out, uint32_t **vals_out, const uint64_t *first_src = nullptr, bool identity_vals = false,
                          const uint32_t *n_dev = nullptr /* the length is *n_dev on the device and `n` its upper bound */, RadixBounds bnd = RadixBounds{});
 int exclusive_scan_u32(elp_ctx *c, const uint32_t *in, uint32_t *out, uint64_t n, uint32_t *total_host /* may be null */);
-int ensure_adapted(elp_ctx *c, bool check_quals = true);  // sort.hip: keys and scores valid (the whole adapt stage if either is missing)
-int ensure_keys(elp_ctx *c);                               // sort.hip: the keys valid - all the coordinate sort asks for
+int ensure_adapted(elp_ctx *c, bool check_quals = true);  // adapt.hip: keys and scores valid (the whole adapt stage if either is missing)
+int ensure_keys(elp_ctx *c);                               // adapt.hip: the keys valid - all the coordinate sort asks for
 // the two halves of ensure_adapted for a caller that computes the fixed-field part (unclipped positions, sort keys) itself - mark
 // duplicates' front pass, markdup.hip: adapt_begin = buffers, key width (*pos_bits), the error word's fill, derived.adapt_begins();
 // adapt_scores = the score kernel (every record's score and low-quality-tail bounds).  The caller sets c->derived.keys and
@@ -518,9 +518,9 @@ int side_join(elp_ctx *c, int lane);                 // ctx.hip: c->stream waits
 int sort_presort(elp_ctx *c);                        // sort.hip: the sort's key passes queued on lane 1 behind what c->stream holds now (elp_sort_ahead)
 void prof_merge_side(elp_ctx *c);          // ctx.hip: the side lane's launch times join the context's
 constexpr int ADAPT_WORDS = 6;
-void adapt_note(elp_ctx *c, const uint32_t *words /* ADAPT_WORDS of adapt_err */);  // sort.hip: the score kernel's words were read (by whoever synchronised anyway)
+void adapt_note(elp_ctx *c, const uint32_t *words /* ADAPT_WORDS of adapt_err */);  // adapt.hip: the score kernel's words were read (by whoever synchronised anyway)
 int adapt_quality_error(elp_ctx *c);
-int ensure_uniform_len(elp_ctx *c);  // sort.hip: c->uniform_len
+int ensure_uniform_len(elp_ctx *c);  // adapt.hip: c->uniform_len
 int ensure_qual_present(elp_ctx *c, bool exact = false);  // exact: scan the whole column instead of a sample
 int fetch_err(elp_ctx *c, uint32_t *words /* 4 */);
 int radix_check(elp_ctx *c);  // reads the error words if radix passes were queued since they were last read

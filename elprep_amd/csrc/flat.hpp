@@ -29,7 +29,7 @@ struct FlatLds {
   uint32_t off[RMAX + 4];  // QUAL offsets of the group's reads minus the first one's (n+1 used; sized to keep LDS 16-byte aligned)
 };
 
-int ensure_flat_index(elp_ctx *c);  // builds c->tile_first for the staged QUAL column (sort.hip)
+int ensure_flat_index(elp_ctx *c);  // builds c->tile_first for the staged QUAL column (adapt.hip)
 
 // ------------------------------------------------------------------ nibble-space helpers
 constexpr uint64_t NIB1 = 0x1111111111111111ull;

@@ -841,7 +841,7 @@ __global__ __launch_bounds__(MF_THREADS) void k_md_front(FrontCols m, const int3
   uint8_t cd = MC_NONE;
   if (mine_rec) {
     if (ADAPT) {
-      // CoordinateLess primary key (k_adapt_fixed, sort.hip): REFID with unmapped behind the last contig and the records that are not sorted
+      // CoordinateLess primary key (k_adapt_fixed, adapt.hip): REFID with unmapped behind the last contig and the records that are not sorted
       // at all behind those, POS, strand
       const uint64_t ru = sta ? (uint64_t)m.n_ref + 1 : (r < 0 ? (uint64_t)m.n_ref : (uint64_t)(uint32_t)r);
       key_out[i] = (ru << (m.pos_bits + 1)) | ((uint64_t)(uint32_t)p << 1) | ((fa_st & F_REVERSED) ? 1ull : 0ull);

@@ -4,7 +4,7 @@
 // output (has_sr column != 0: sr-tagged copies, records rejected by elp_filter_records) go behind the others, in the same order.
 //
 // Every record is a member of one tie group whose comparator is the name alone, so the coordinate sort's tie-break (sort.hip) is run
-// over the whole read set, without its keys:
+// over the whole read set, without its keys (the rank tables and the packing of the keys are the same host code, sort_plan.hpp):
 //   (1) k_qn_values: one sweep over the names, eight bytes per load, zero-padded to the longest name: the set of byte values that occur
 //       at every position (256 bits per position, in LDS); positions with more than one value are live.  One read-back.
 //   (2) k_qn_keys: a 64-bit key per record = {state, ranks of its bytes at the most significant live positions} (a rank takes as few
@@ -19,12 +19,12 @@
 #include <vector>
 
 #include "common.hpp"
+#include "sort_plan.hpp"  // QN_STATE, QN_LEN; the fields, their ranks and the cuts of the rounds
 
 namespace elp {
 
-// fields of a key, most significant first: pos[j] < QN_STATE is a byte position (rank = lut[slot[j] * 256 + padded byte]), QN_STATE the
+// fields of a key, most significant first: pos[j] < QN_LEN is a byte position (rank = lut[slot[j] * 256 + padded byte]), QN_STATE the
 // record state (not output = 1), QN_LEN the name length; field j sits at bit shift[j]
-constexpr uint16_t QN_STATE = 0xFFFF, QN_LEN = 0xFFFE;
 struct QnFields { uint16_t pos[64]; uint16_t slot[64]; uint8_t shift[64]; uint32_t n; };
 constexpr uint32_t QN_CAP = 64;  // largest group of equal keys ranked by comparison (all pairs)
 
@@ -123,107 +123,108 @@ __global__ __launch_bounds__(256) void k_qn_ties(uint64_t n, const uint64_t *__r
   perm[s + rank] = me;
 }
 
-// the queryname sort of c's records into c->perm, on c's stream (c: the side lane's shadow context, sort_queryname below)
-static int qname_sort_impl(elp_ctx *c) {
-  const uint64_t n = c->n;
-  if (n == 0) return 0;
-  const uint32_t maxq = c->max_qname_len;  // <= MAX_QNAME (elp_stage enforces it)
-  // scratch slots 1 .. 3: slot 0 of the sort lane holds the coordinate key passes made ahead (elp_sort_ahead), which stay valid
+// What the phases of one queryname sort hand on.  Scratch slots 1 .. 3 of the lane (sort_plan.hpp: slot 0 holds the coordinate key
+// passes made ahead, elp_sort_ahead, which stay valid).
+struct QnWork {
+  uint64_t n;
+  uint32_t maxq;  // <= MAX_QNAME (elp_stage enforces it)
+  QnScratch lay;
+  uint64_t *k0 = nullptr, *k1 = nullptr;
+  uint32_t *vcur = nullptr, *vtmp = nullptr;
+  uint32_t *d_vals = nullptr, *d_over = nullptr;
+  uint8_t *d_lut = nullptr;
+  const uint64_t *qoff = nullptr;
+  const uint8_t *q = nullptr, *state = nullptr;
+  QnWork(uint64_t records, uint32_t longest) : n(records), maxq(longest), lay(longest) {}
+};
+
+static QnFields qn_packed(const RankFields &f, FieldCut cut) {
+  QnFields p;
+  memset(&p, 0, sizeof p);
+  for (int k = cut.lo; k < cut.hi; k++, p.n++) { p.pos[p.n] = f.pos[k]; p.slot[p.n] = f.slot[k]; }
+  field_shifts(f.bits, cut, p.shift);
+  return p;
+}
+
+// (1) the values at every position: one kernel, one read-back; from them the key's fields and the rank LUT
+static int qn_tables(elp_ctx *c, QnWork &w, RankFields *f) {
+  const SortScratch sc(w.n);
   uint64_t *kbuf;
   uint32_t *vbuf, *small;
-  ELP_TRY(scratch(c, 1, 2 * n + 8, &kbuf));
-  ELP_TRY(scratch(c, 2, 2 * n + 8, &vbuf));
-  const size_t vwords = (size_t)maxq * 8 + 1, lut_words = ((size_t)maxq * 256 + 3) / 4;
-  ELP_TRY(scratch(c, 3, vwords + 1 + lut_words, &small));
-  uint32_t *d_vals = small, *d_over = small + vwords;
-  uint8_t *d_lut = reinterpret_cast<uint8_t *>(small + vwords + 1);
-  const uint64_t *qoff = c->qname_off.p;
-  const uint8_t *q = c->qname.p, *state = c->has_sr.p;
-  // (1) the values at every position: one kernel, one read-back
-  std::vector<uint32_t> hv(vwords, 0);
-  if (maxq > 0) {
-    ELP_HIP(c, hipMemsetAsync(d_vals, 0, (vwords + 1) * 4, c->stream));
-    const unsigned grid = std::min<unsigned>(blocks_for(n, 256), (unsigned)c->n_cu * 4);
-    ELP_LAUNCH(c, "qn_values", k_qn_values, dim3(grid), dim3(256), (size_t)maxq * 8 * 4, n, qoff, q, maxq, d_vals);
-    ELP_HIP(c, hipMemcpyAsync(hv.data(), d_vals, vwords * 4, hipMemcpyDeviceToHost, c->stream));
+  ELP_TRY(scratch(c, 1, sc.keys, &kbuf));
+  ELP_TRY(scratch(c, 2, sc.vals, &vbuf));
+  ELP_TRY(scratch(c, 3, w.lay.words3, &small));
+  w.k0 = kbuf; w.k1 = kbuf + w.n;
+  w.vcur = vbuf; w.vtmp = vbuf + w.n;
+  w.d_vals = small; w.d_over = small + w.lay.d_over;
+  w.d_lut = reinterpret_cast<uint8_t *>(small + w.lay.d_lut);
+  w.qoff = c->qname_off.p; w.q = c->qname.p; w.state = c->has_sr.p;
+  std::vector<uint32_t> hv(w.lay.vwords, 0);
+  if (w.maxq > 0) {
+    ELP_HIP(c, hipMemsetAsync(w.d_vals, 0, (w.lay.vwords + 1) * 4, c->stream));
+    const unsigned grid = std::min<unsigned>(blocks_for(w.n, 256), (unsigned)c->n_cu * 4);
+    ELP_LAUNCH(c, "qn_values", k_qn_values, dim3(grid), dim3(256), (size_t)w.maxq * 8 * 4, w.n, w.qoff, w.q, w.maxq, w.d_vals);
+    ELP_HIP(c, hipMemcpyAsync(hv.data(), w.d_vals, w.lay.vwords * 4, hipMemcpyDeviceToHost, c->stream));
     ELP_HIP(c, elp::stream_wait(c->stream));
   } else {
-    ELP_HIP(c, hipMemsetAsync(d_over, 0, 4, c->stream));
+    ELP_HIP(c, hipMemsetAsync(w.d_over, 0, 4, c->stream));
   }
-  // the fields, most significant first: the state (if any record is not output), the live positions (ranks), the length (if a name
-  // holds a NUL byte)
-  std::vector<uint16_t> fpos, fslot;
-  std::vector<int> fbits;
-  if (c->n_sr > 0) { fpos.push_back(QN_STATE); fslot.push_back(0); fbits.push_back(1); }
-  std::vector<uint8_t> lut;
-  uint32_t nlive = 0;
-  for (uint32_t p = 0; p < maxq; p++) {
-    int cnt = 0;
-    for (int w = 0; w < 8; w++) cnt += __builtin_popcount(hv[(size_t)p * 8 + w]);
-    if (cnt < 2) continue;
-    lut.resize((size_t)(nlive + 1) * 256, 0);
-    int rank = 0;
-    for (int v = 0; v < 256; v++)
-      if ((hv[(size_t)p * 8 + (v >> 5)] >> (v & 31)) & 1u) lut[(size_t)nlive * 256 + v] = (uint8_t)rank++;
-    int b = 1;
-    while ((1 << b) < rank) b++;
-    fpos.push_back((uint16_t)p); fslot.push_back((uint16_t)nlive); fbits.push_back(b);
-    nlive++;
-  }
-  if (maxq > 0 && hv[(size_t)maxq * 8]) { fpos.push_back(QN_LEN); fslot.push_back(0); fbits.push_back(11); }  // lengths <= MAX_QNAME < 2^11
-  if (!lut.empty()) ELP_HIP(c, hipMemcpyAsync(d_lut, lut.data(), lut.size(), hipMemcpyHostToDevice, c->stream));
-  const int nf = (int)fpos.size();
-  // fields [lo, hi) as one key, packed below bit 64 (lower fields in lower bits)
-  auto pack = [&](int lo, int hi, int *total) {
-    QnFields f;
-    memset(&f, 0, sizeof f);
-    int sh = 0;
-    for (int k = lo; k < hi; k++) sh += fbits[k];
-    *total = sh;
-    for (int k = lo; k < hi; k++) {
-      sh -= fbits[k];
-      f.pos[f.n] = fpos[k]; f.slot[f.n] = fslot[k]; f.shift[f.n] = (uint8_t)sh;
-      f.n++;
-    }
-    return f;
-  };
-  uint64_t *k0 = kbuf, *k1 = kbuf + n;
-  uint32_t *vcur = vbuf, *vtmp = vbuf + n;
-  const unsigned g = blocks_for(n, 256);
-  // (2) one key of the most significant fields that fit
-  int hi = 0, bits = 0;
-  while (hi < nf && hi < 64 && bits + fbits[hi] <= 64) bits += fbits[hi++];
-  const bool settled = hi == nf;
-  int total = 0;
-  QnFields f = pack(0, hi, &total);
-  ELP_LAUNCH(c, "qn_keys", k_qn_keys, dim3(g), dim3(256), 0, n, (const uint32_t *)nullptr, f, (const uint8_t *)d_lut, qoff, q, state, k0);
-  uint64_t *ko;
-  uint32_t *vo;
-  ELP_TRY(radix_sort_pairs_low(c, k0, vcur, k1, vtmp, n, (total + 7) / 8, &ko, &vo, nullptr, true));
-  c->radix_check_pending = true;  // (read by the caller: radix_check)
-  // (3) the groups of equal keys, into the permutation
-  ELP_LAUNCH(c, "qn_ties", k_qn_ties, dim3(g), dim3(256), 0, n, (const uint64_t *)ko, (const uint32_t *)vo, c->perm.p, qoff, q,
-             (uint32_t)settled, d_over);
-  if (settled) return 0;
-  uint32_t h_over = 0;
-  ELP_HIP(c, hipMemcpyAsync(&h_over, d_over, 4, hipMemcpyDeviceToHost, c->stream));
-  ELP_HIP(c, elp::stream_wait(c->stream));
-  if (!h_over) return 0;
-  // a group of more than QN_CAP equal keys: stable LSD rounds over every field, least significant first, from staging order
-  const uint32_t *order = nullptr;
-  for (int top = nf; top > 0;) {
-    int lo = top, tb = 0;
-    while (lo > 0 && tb + fbits[lo - 1] <= 64 && top - lo < 64) tb += fbits[--lo];
-    QnFields fr = pack(lo, top, &total);
-    ELP_LAUNCH(c, "qn_keys", k_qn_keys, dim3(g), dim3(256), 0, n, order, fr, (const uint8_t *)d_lut, qoff, q, state, k0);
-    ELP_TRY(radix_sort_pairs_low(c, k0, vcur, k1, vtmp, n, (total + 7) / 8, &ko, &vo, nullptr, order == nullptr));
-    if (vo != vcur) std::swap(vcur, vtmp);
-    order = vcur;
-    top = lo;
-  }
-  ELP_LAUNCH(c, "qn_ties", k_qn_ties, dim3(g), dim3(256), 0, n, (const uint64_t *)k0, (const uint32_t *)vcur, c->perm.p, qoff, q, 1u, d_over);
+  *f = qn_fields(hv.data(), w.maxq, c->n_sr > 0);
+  if (!f->lut.empty()) ELP_HIP(c, hipMemcpyAsync(w.d_lut, f->lut.data(), f->lut.size(), hipMemcpyHostToDevice, c->stream));
   return 0;
 }
+
+// (2) one key of the most significant fields that fit, (3) the groups of equal keys, into the permutation.  *done = the permutation
+// stands; else a group of more than QN_CAP equal keys was found
+static int qn_key_round(elp_ctx *c, QnWork &w, const RankFields &f, bool *done) {
+  const unsigned g = blocks_for(w.n, 256);
+  const FieldCut cut = pack_prefix(f.bits, 0);
+  const bool settled = cut.hi == f.n();
+  const QnFields p = qn_packed(f, cut);
+  ELP_LAUNCH(c, "qn_keys", k_qn_keys, dim3(g), dim3(256), 0, w.n, (const uint32_t *)nullptr, p, (const uint8_t *)w.d_lut, w.qoff, w.q, w.state, w.k0);
+  uint64_t *ko;
+  uint32_t *vo;
+  ELP_TRY(radix_sort_pairs_low(c, w.k0, w.vcur, w.k1, w.vtmp, w.n, key_digits(cut.total), &ko, &vo, nullptr, true));
+  c->radix_check_pending = true;  // (read by the caller: radix_check)
+  ELP_LAUNCH(c, "qn_ties", k_qn_ties, dim3(g), dim3(256), 0, w.n, (const uint64_t *)ko, (const uint32_t *)vo, c->perm.p, w.qoff, w.q,
+             (uint32_t)settled, w.d_over);
+  *done = settled;
+  if (settled) return 0;
+  uint32_t h_over = 0;
+  ELP_HIP(c, hipMemcpyAsync(&h_over, w.d_over, 4, hipMemcpyDeviceToHost, c->stream));
+  ELP_HIP(c, elp::stream_wait(c->stream));
+  *done = !h_over;
+  return 0;
+}
+
+// a group of more than QN_CAP equal keys: stable LSD rounds over every field, least significant first, from staging order
+static int qn_lsd_rounds(elp_ctx *c, QnWork &w, const RankFields &f) {
+  const unsigned g = blocks_for(w.n, 256);
+  const uint32_t *order = nullptr;
+  for (const FieldCut &cut : lsd_cuts(f.bits)) {
+    const QnFields p = qn_packed(f, cut);
+    ELP_LAUNCH(c, "qn_keys", k_qn_keys, dim3(g), dim3(256), 0, w.n, order, p, (const uint8_t *)w.d_lut, w.qoff, w.q, w.state, w.k0);
+    uint64_t *ko;
+    uint32_t *vo;
+    ELP_TRY(radix_sort_pairs_low(c, w.k0, w.vcur, w.k1, w.vtmp, w.n, key_digits(cut.total), &ko, &vo, nullptr, order == nullptr));
+    if (vo != w.vcur) std::swap(w.vcur, w.vtmp);
+    order = w.vcur;
+  }
+  ELP_LAUNCH(c, "qn_ties", k_qn_ties, dim3(g), dim3(256), 0, w.n, (const uint64_t *)w.k0, (const uint32_t *)w.vcur, c->perm.p, w.qoff, w.q, 1u, w.d_over);
+  return 0;
+}
+
+// the queryname sort of c's records into c->perm, on c's stream (c: the side lane's shadow context, sort_queryname below)
+static int qname_sort_impl(elp_ctx *c) {
+  if (c->n == 0) return 0;
+  QnWork w(c->n, c->max_qname_len);
+  RankFields f;
+  ELP_TRY(qn_tables(c, w, &f));
+  bool done = false;
+  ELP_TRY(qn_key_round(c, w, f, &done));
+  return done ? 0 : qn_lsd_rounds(c, w, f);
+}
+
 
 // On the context's side lane 1, as the coordinate sort (sort.hip, sort_on_side): the shadow sees the name columns, the state column and
 // the permutation's buffer as views for the duration of the call.  Nothing of the adapt stage (keys, scores) is read or made.

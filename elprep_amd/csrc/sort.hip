@@ -1,7 +1,6 @@
-// sort.hip — adapt (unclipped position, Phred-sum score, coordinate key) and the coordinate sort.
+// sort.hip — the coordinate sort (its key column is the adapt stage's, adapt.hip).
 //
-// Reference: sam.CoordinateLess + modFlag (sam/sam-types.go:408-473), By.ParallelStableSort (:639-641),
-// computeUnclippedPosition / computePhredScore (filters/mark-duplicates.go:57-110).
+// Reference: sam.CoordinateLess + modFlag (sam/sam-types.go:408-473), By.ParallelStableSort (:639-641).
 //
 // Sort = (1) 64-bit primary key {refid (unmapped last), POS, strand} sorted by the LSD radix sort of radix.hip,
 //        (2) tie resolution inside runs of equal primary key with the comparator tail
@@ -9,531 +8,15 @@
 //            runs <= TIE_SMALL records: every record computes its rank in the run directly (all-pairs);
 //            larger runs (the unmapped block, pile-ups): LSD radix over the live bytes of the zero-padded comparator string,
 //            8 bytes per round, then one stable round on the run id.
+// The host's part - key format, run bounds, scratch layout, rank tables, the packing of the rounds' keys - is sort_plan.hpp's: the
+// phases at the end of this file launch and copy, and compute no size, offset, width or cut themselves.
+#include <algorithm>
 #include <cstdlib>
 
-#include "apply_rec.hpp"
 #include "common.hpp"
-#include "flat.hpp"
+#include "sort_plan.hpp"  // TIE_SMALL, TIE_MAX_PACKED
 
 namespace elp {
-
-constexpr int TIE_SMALL = 48;
-
-// ------------------------------------------------------------------ adapt
-// fixed-field part: unclipped 5' position (computeUnclippedPosition :79-110) and the CoordinateLess primary key
-__global__ __launch_bounds__(256) void k_adapt_fixed(uint64_t n, const int32_t *__restrict__ pos, const int32_t *__restrict__ refid,
-                                                     const uint16_t *__restrict__ flag, const uint64_t *__restrict__ cigar_off,
-                                                     const uint32_t *__restrict__ cigar, int32_t *__restrict__ upos, int32_t *__restrict__ score,
-                                                     uint64_t *__restrict__ key, uint32_t n_ref, int pos_bits,
-                                                     const uint8_t *__restrict__ has_sr) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint16_t f = flag[i];
-  const int32_t p = pos[i];
-  const int32_t r = refid[i];
-  // CoordinateLess primary key: REFID ascending with negative last (:429-432), POS (:433-436), forward before reverse (:437-438)
-  // The key is packed into as few bits as the data needs (unmapped = one code above the last contig; POS in pos_bits bits, the
-  // width of the largest staged POS), so that the LSD radix sort has as few live digit positions as possible.
-  // Records with the sr tag are dropped behind the mark-duplicates filter (RemoveOptionalReads, cmd/filter.go:803) and never reach
-  // the sort: they get one more code above "unmapped", i.e. the tail of the permutation (elp_num_sorted()).
-  const uint64_t ru = has_sr[i] ? (uint64_t)n_ref + 1 : (r < 0 ? (uint64_t)n_ref : (uint64_t)(uint32_t)r);
-  key[i] = (ru << (pos_bits + 1)) | ((uint64_t)(uint32_t)p << 1) | ((f & F_REVERSED) ? 1ull : 0ull);
-  int32_t up = 0;
-  if ((f & (F_UNMAPPED | F_SECONDARY | F_SUPPLEMENTARY)) == 0) {  // mark-duplicates.go:427,436
-    const uint64_t c0 = cigar_off[i], c1 = cigar_off[i + 1];
-    up = p;
-    if (c1 > c0) {
-      if (f & F_REVERSED) {  // :90-100
-        int32_t clipped = 1;
-        up--;
-        for (uint64_t k = c1; k-- > c0;) {
-          const uint32_t c = cigar[k];
-          const uint32_t op = c & 0xF;
-          const int32_t isclip = (op == OP_S || op == OP_H) ? 1 : 0;
-          const int32_t isref = op_consumes_ref(op) ? 1 : 0;
-          clipped *= isclip;
-          up += (isref | clipped) * (int32_t)(c >> 4);
-        }
-      } else {  // :101-108
-        for (uint64_t k = c0; k < c1; k++) {
-          const uint32_t c = cigar[k];
-          const uint32_t op = c & 0xF;
-          if (!(op == OP_S || op == OP_H)) break;
-          up -= (int32_t)(c >> 4);
-        }
-      }
-    }
-  }
-  upos[i] = up;
-  score[i] = 0;
-}
-
-// byte mask (0xFF per byte) for the first n bytes (n unclamped) of a 32-bit word
-__device__ __forceinline__ uint32_t first_bytes32(int n) { return n <= 0 ? 0u : (n >= 4 ? 0xFFFFFFFFu : (0xFFFFFFFFu >> (32 - 8 * n))); }
-
-// computePhredScore :57-68 as a flat stream over the QUAL column: sum of qualities >= 15 per duplicate-marking candidate;
-// any quality > 93 in a candidate is an error.  SWAR over the lane's 16 bytes, v_sad_u8 for the byte sums.
-struct ScoreBody {
-  static constexpr int NT = FL_THREADS, TILES = 4, RMAX = 1024;
-  static constexpr bool TILE_ENDS = false;
-  const uint16_t *__restrict__ flag;
-  const uint8_t *__restrict__ qual;
-  int32_t *score;
-  uint64_t *qbounds;
-  int32_t *acc;    // LDS [RMAX]: per-read partial sums of this group (LDS atomics; one global store per read)
-  uint32_t *lo;    // LDS [RMAX]: index of the first quality > 2 of the read (0xFFFFFFFF: none yet)
-  uint32_t *hi;    // LDS [RMAX]: 1 + index of the last quality > 2 (0: none yet)
-  uint8_t *cand;   // LDS [RMAX]: duplicate-marking candidate?
-  const uint4 *mask;  // LDS [17]: byte masks of the first nb bytes of a block, one 16-byte read instead of sixteen instructions
-  uint32_t bad;
-
-  __device__ __forceinline__ void stage(uint32_t g0, uint32_t ng) {
-    for (uint32_t k = threadIdx.x; k < ng; k += NT) {
-      acc[k] = 0;
-      lo[k] = 0xFFFFFFFFu;
-      hi[k] = 0u;
-      cand[k] = (flag[g0 + k] & (F_UNMAPPED | F_SECONDARY | F_SUPPLEMENTARY)) == 0;
-    }
-  }
-  // Byte tests of a word by ONE add: for bytes below 128 - 113 (every legal quality is) adding 113 / 125 / 34 sets bit 7 of exactly the
-  // bytes >= 15 / > 2 / >= 94 without a carry into the next byte; a byte that does carry is >= 94 in the first place and is reported as
-  // such (`bad`, checked on the same word).  The words are masked to the block's bytes first, so no test needs the mask again.
-  static __device__ __forceinline__ uint32_t part(uint32_t x, uint32_t s) {  // s + the sum of the bytes >= 15
-    const uint32_t ge15 = ((x + 0x71717171u) & 0x80808080u) >> 7;
-    return __builtin_amdgcn_sad_u8(x & (ge15 * 0xFFu), 0u, s);
-  }
-  static __device__ __forceinline__ uint32_t gt2(uint32_t x) { return (((x | 0x80808080u) - 0x03030303u) | x) & 0x80808080u; }  // bit 7 of every byte > 2, whatever the bytes (a missing-QUAL filler of 0xFF in a non-candidate must not spill into its neighbour's test)
-  static __device__ __forceinline__ uint32_t ge94(uint32_t x) { return x | (x + 0x22222222u); }           // bit 7 of every byte >= 94 (or >= 128)
-  struct Pre { Chunk ch; uint32_t rl; int nb; int k0; };
-  __device__ __forceinline__ bool prefetch(uint32_t rl, int k0, int nb, uint64_t qpos, uint32_t, Pre &p) {
-    p.rl = rl; p.nb = nb; p.k0 = k0;
-    p.ch.load(qual + qpos);
-    return true;
-  }
-  __device__ __forceinline__ void process(Pre &p) {
-    const uint4 mk = mask[p.nb];
-    const uint32_t x0 = p.ch.w0 & mk.x, x1 = p.ch.w1 & mk.y, x2 = p.ch.w2 & mk.z, x3 = p.ch.w3 & mk.w;
-    // low-quality-tail bounds: first / last quality > 2 of the read
-    const uint64_t glo = (uint64_t)gt2(x0) | ((uint64_t)gt2(x1) << 32);
-    const uint64_t ghi = (uint64_t)gt2(x2) | ((uint64_t)gt2(x3) << 32);
-    if (glo | ghi) {
-      const int first = glo ? (__builtin_ctzll(glo) >> 3) : 8 + (__builtin_ctzll(ghi) >> 3);
-      const int last = ghi ? 8 + ((63 - __builtin_clzll(ghi)) >> 3) : ((63 - __builtin_clzll(glo)) >> 3);
-      atomicMin(&lo[p.rl], (uint32_t)(p.k0 + first));
-      atomicMax(&hi[p.rl], (uint32_t)(p.k0 + last + 1));
-    }
-    if (!cand[p.rl]) return;
-    // a quality >= 94 (or a byte whose carry could have spoilt a neighbour's test) in a duplicate-marking candidate: the error bit
-    bad |= (ge94(x0) | ge94(x1) | ge94(x2) | ge94(x3)) & 0x80808080u;
-    const uint32_t s = part(x3, part(x2, part(x1, part(x0, 0u))));
-    if (s) atomicAdd(&acc[p.rl], (int32_t)s);
-  }
-  __device__ __forceinline__ void group_end(uint32_t g0, uint32_t ng) {
-    for (uint32_t k = threadIdx.x; k < ng; k += NT) {  // a read belongs to exactly one group
-      score[g0 + k] = acc[k];
-      qbounds[g0 + k] = (uint64_t)hi[k] | ((uint64_t)lo[k] << 32);  // all-zero = no quality > 2
-    }
-  }
-  __device__ __forceinline__ void slots(uint32_t) {}
-  __device__ __forceinline__ void retire() {}
-  __device__ __forceinline__ void tile_end(uint32_t, uint64_t) {}
-};
-
-__global__ __launch_bounds__(FL_THREADS) void k_score_flat(uint64_t n, const uint64_t *__restrict__ qual_off, const uint8_t *__restrict__ qual,
-                                                           uint64_t qual_bytes, const uint32_t *__restrict__ tile_first,
-                                                           const uint16_t *__restrict__ flag, int32_t *score, uint64_t *qbounds, uint32_t *err) {
-  __shared__ FlatLds<ScoreBody::RMAX> L;
-  __shared__ int32_t acc[ScoreBody::RMAX];
-  __shared__ uint32_t lo[ScoreBody::RMAX], hi[ScoreBody::RMAX];
-  __shared__ uint8_t cand[ScoreBody::RMAX];
-  __shared__ uint4 mask[17];
-  if (threadIdx.x <= 16) {
-    const int nb = (int)threadIdx.x;
-    mask[nb] = make_uint4(first_bytes32(nb), first_bytes32(nb - 4), first_bytes32(nb - 8), first_bytes32(nb - 12));
-  }
-  __syncthreads();
-  ScoreBody B{flag, qual, score, qbounds, acc, lo, hi, cand, mask, 0u};
-  flat_run(qual_off, n, qual_bytes, tile_first, L, B);
-  if (__any(B.bad != 0) && (threadIdx.x & 63) == 0) atomicOr(&err[0], 1u);
-}
-
-// computePhredScore + the low-quality-tail bounds for read sets of ONE length (what a sequencer writes; ensure_uniform_len): a READ per
-// lane.  A wave copies the QUAL bytes of 64 consecutive reads - one contiguous, 64-byte-aligned span - into its own LDS tile with
-// coalesced 16-byte loads and every lane then walks the words of its read: the sums, the error test and the positions of the first /
-// last quality > 2 stay in the lane's registers.  k_score_flat spreads a read over ~10 lanes and combines them through three LDS
-// atomics per 16-byte block on the read's cells (PMC, round 3: 79 % of its LDS cycles were bank conflicts of exactly those).
-constexpr int SU_WAVES = 8, SU_MAX_LEN = 250;  // a read touches at most 64 words (the bitmap of words with a quality > 2)
-__device__ __forceinline__ uint32_t su_gt2(uint32_t x) { return (((x | 0x80808080u) - 0x03030303u) | x) & 0x80808080u; }  // bit 7 of every byte > 2, any byte value
-template <int R>
-__global__ __launch_bounds__(64 * SU_WAVES) void k_score_uniform(uint64_t n, uint32_t L, const uint8_t *__restrict__ qual, const uint16_t *__restrict__ flag,
-                                                                 int32_t *__restrict__ score, uint64_t *__restrict__ qbounds, uint32_t *err,
-                                                                 uint32_t qstride /* every qstride-th group of 64 reads notes the quality values it holds */,
-                                                                 unsigned long long *qmask, const uint16_t *__restrict__ rgid, const uint16_t *__restrict__ rg_cov,
-                                                                 uint2 *__restrict__ arecs /* not null: ApplyBQSR's per-read records (apply_rec.hpp) */) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t su_lds[];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t tile_bytes = 64u * L, tile_words = tile_bytes / 4u + 4u;
-  uint32_t *tile = su_lds + (size_t)wave * tile_words;
-  const uint32_t s = lane * L, w0 = s >> 2, skip = s & 3u;  // the read's first word and the bytes of it in front of the read
-  const uint32_t nw = (skip + L + 3u) >> 2, tail = (skip + L) & 3u;
-  const uint32_t m_first = 0xFFFFFFFFu << (8u * skip), m_last = tail ? 0xFFFFFFFFu >> (32u - 8u * tail) : 0xFFFFFFFFu;
-  uint32_t bad = 0;
-  uint32_t qm[3] = {0, 0, 0};  // bits 0 .. 95: quality values seen by the sampled groups (the BQSR gather's sizing hint, ensure_qual_present)
-  const uint64_t ngroups = (n + 63) / 64;
-  for (uint64_t g = (uint64_t)blockIdx.x * SU_WAVES + wave; g < ngroups; g += (uint64_t)gridDim.x * SU_WAVES) {
-    const uint64_t r0 = g * 64;
-    const uint8_t *base = qual + r0 * L;
-    const uint64_t have = (n - r0 < 64 ? n - r0 : 64) * (uint64_t)L;  // the last group may be short
-    uint4 v[R];
-#pragma unroll
-    for (int k = 0; k < R; k++) {
-      const uint32_t off = (uint32_t)k * 1024u + lane * 16u;
-      v[k] = make_uint4(0u, 0u, 0u, 0u);
-      if (off < have) v[k] = *reinterpret_cast<const uint4 *>(base + off);  // (the column is padded: the last chunk may read past `have`)
-    }
-#pragma unroll
-    for (int k = 0; k < R; k++) {
-      const uint32_t off = (uint32_t)k * 1024u + lane * 16u;
-      if (off < tile_bytes) *reinterpret_cast<uint4 *>(tile + off / 4u) = v[k];
-    }
-    // (the tile is the wave's own, and a wave's LDS operations execute in order: no barrier)
-    const uint64_t r = r0 + lane;
-    if (r < n) {
-      const uint16_t f = flag[r];
-      const bool cand = (f & (F_UNMAPPED | F_SECONDARY | F_SUPPLEMENTARY)) == 0;
-      const uint16_t rg = arecs ? rgid[r] : (uint16_t)ELP_NIL16;
-      const uint32_t *rw = tile + w0;
-      uint32_t x = rw[0] & m_first;
-      if (nw == 1) x &= m_last;
-      // per word: the sum of the bytes >= 15 (six operations), the OR of all words (the > 93 test is made ONCE on it: a byte of the OR is
-      // at least the byte of every word, so a clean OR clears the read - legal qualities stay below 64, whose ORs stay below 94 - and only a
-      // flagged OR is looked at word by word), and the first / last word that holds a quality > 2 as two running indices (round 6: five
-      // vector instructions fewer per word than a 64-bit bitmap of such words and a > 93 test per word; measured on the same box: no change
-      // in the kernel's time - 73 % vector issue by PMC, but the LDS tile's round trip is what a wave waits for)
-      constexpr uint32_t NONE = 0xFFFFFFFFu;
-      uint32_t sum = ScoreBody::part(x, 0u), orx = x;
-      uint32_t kf = su_gt2(x) ? 0u : NONE, kl = 0u;
-#pragma unroll 8
-      for (uint32_t k = 1; k + 1 < nw; k++) {
-        x = rw[k];
-        sum = ScoreBody::part(x, sum);
-        orx |= x;
-        const bool gk = su_gt2(x) != 0u;
-        kf = min(kf, gk ? k : NONE);
-        kl = gk ? k : kl;
-      }
-      if (nw > 1) {
-        x = rw[nw - 1] & m_last;
-        sum = ScoreBody::part(x, sum);
-        orx |= x;
-        const bool gk = su_gt2(x) != 0u;
-        kf = min(kf, gk ? nw - 1 : NONE);
-        kl = gk ? nw - 1 : kl;
-      }
-      uint32_t bd = ScoreBody::ge94(orx) & 0x80808080u;
-      if (bd) {  // (rare) exactly, word by word
-        bd = 0;
-        for (uint32_t k = 0; k < nw; k++) {
-          uint32_t xw = rw[k];
-          if (k == 0) xw &= m_first;
-          if (k == nw - 1) xw &= m_last;
-          bd |= ScoreBody::ge94(xw);
-        }
-      }
-      uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-      if (kf != NONE) {
-        uint32_t xf = rw[kf], xl = rw[kl];
-        if (kf == 0) xf &= m_first;
-        if (kf == nw - 1) xf &= m_last;
-        if (kl == 0) xl &= m_first;
-        if (kl == nw - 1) xl &= m_last;
-        lo = kf * 4u + ((uint32_t)__builtin_ctz(su_gt2(xf)) >> 3) - skip;
-        hi = kl * 4u + ((31u - (uint32_t)__builtin_clz(su_gt2(xl))) >> 3) - skip + 1u;
-      }
-      score[r] = cand ? (int32_t)sum : 0;
-      qbounds[r] = (uint64_t)hi | ((uint64_t)lo << 32);
-      if (cand) bad |= bd & 0x80808080u;
-      if (arecs) arecs[r] = rg == ELP_NIL16 ? make_uint2(AR_NO_RG, 0u) : apply_record(L, (int)L, f, (uint64_t)hi | ((uint64_t)lo << 32), rg_cov[rg]);
-      if ((uint32_t)g % qstride == 0) {  // (wave-uniform)
-        for (uint32_t k = 0; k < nw; k++) {
-          const uint32_t vm = (k == 0 ? m_first : 0xFFFFFFFFu) & (k + 1 == nw ? m_last : 0xFFFFFFFFu), xw = rw[k];
-#pragma unroll
-          for (int b = 0; b < 4; b++) {
-            const uint32_t q = (xw >> (8 * b)) & 0xFFu, bit = ((vm >> (8 * b)) & 1u) << (q & 31u), ws = q >> 5;
-            qm[0] |= ws == 0 ? bit : 0u;
-            qm[1] |= ws == 1 ? bit : 0u;
-            qm[2] |= ws == 2 ? bit : 0u;
-          }
-        }
-      }
-    }
-  }
-  if (__any(bad != 0) && lane == 0) atomicOr(&err[0], 1u);
-  if (__any((qm[0] | qm[1] | qm[2]) != 0)) {
-    for (int d = 32; d >= 1; d >>= 1) {
-      qm[0] |= __shfl_xor(qm[0], d, 64);
-      qm[1] |= __shfl_xor(qm[1], d, 64);
-      qm[2] |= __shfl_xor(qm[2], d, 64);
-    }
-    if (lane == 0) {
-      const unsigned long long lo = (unsigned long long)qm[0] | ((unsigned long long)qm[1] << 32);
-      if (lo) atomicOr(&qmask[0], lo);
-      if (qm[2]) atomicOr(&qmask[1], (unsigned long long)qm[2]);
-    }
-  }
-}
-// LDS bank conflicts of the per-lane walk: lanes are L bytes apart; if that is a whole number of words with a large power of two in it,
-// many lanes sit on one bank - those lengths stay with k_score_flat
-static bool score_uniform_ok(uint32_t L) {
-  if (L < 16 || L > (uint32_t)SU_MAX_LEN) return false;
-  if (L % 4u) return true;
-  return ((L / 4u) % 4u) != 0;  // at most two lanes more per bank than the 64-lanes-on-32-banks minimum
-}
-template <int R>
-static int score_uniform_launch(elp_ctx *c) {
-  const uint32_t L = c->uniform_len;
-  const size_t dyn = (size_t)SU_WAVES * ((size_t)64 * L + 16);
-  const unsigned per_cu = (unsigned)std::max<size_t>(1, (160 * 1024) / (dyn + 256));
-  const uint64_t ngroups = (c->n + 63) / 64;
-  const unsigned grid = (unsigned)std::min<uint64_t>((ngroups + SU_WAVES - 1) / SU_WAVES, (uint64_t)c->n_cu * per_cu);
-  ELP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_score_uniform<R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-  // ApplyBQSR's records on the way (apply3.hip takes whole 16-byte blocks of reads of one length)
-  uint2 *arecs = nullptr;
-  if (L >= 16 && L <= 0x7FFF && c->n_rg > 0) {
-    ELP_TRY(ensure(c, c->apply_recs, c->n + 4));
-    arecs = c->apply_recs.p;
-  }
-  // the sample of the quality values: everything up to ~500 K reads (the hint is then exact, as k_qual_present_sample's is), one group in
-  // up to 128 of longer columns
-  const uint32_t qstride = (uint32_t)std::min<uint64_t>(128, std::max<uint64_t>(1, ngroups / 8192));
-  ELP_LAUNCH(c, "adapt_score", k_score_uniform<R>, dim3(grid), dim3(64 * SU_WAVES), dyn, c->n, L, (const uint8_t *)c->qual.p, (const uint16_t *)c->flag.p,
-             c->score.p, c->qbounds.p, c->adapt_err.p, qstride, reinterpret_cast<unsigned long long *>(c->adapt_err.p + 2), (const uint16_t *)c->rgid.p,
-             (const uint16_t *)c->rg_cov.p, arecs);
-  c->derived.adapt_sampled = true;
-  c->derived.apply_recs_valid = arecs != nullptr;
-  c->apply_recs_lmax = (int)L;
-  return 0;
-}
-static int score_uniform(elp_ctx *c) {
-  switch ((c->uniform_len + 15u) / 16u) {  // 16-byte load rounds of a wave's tile
-#define ELP_SU(R) case R: return score_uniform_launch<R>(c);
-    ELP_SU(1) ELP_SU(2) ELP_SU(3) ELP_SU(4) ELP_SU(5) ELP_SU(6) ELP_SU(7) ELP_SU(8) ELP_SU(9) ELP_SU(10) ELP_SU(11) ELP_SU(12) ELP_SU(13) ELP_SU(14)
-    ELP_SU(15) ELP_SU(16)
-#undef ELP_SU
-  }
-  return set_error(c, ELP_ERR_ARG, "score_uniform: read length %u", c->uniform_len);
-}
-
-// Set of quality values present, from a sample of the tiles (every `stride`-th).  It is a sizing hint for the BQSR gather's
-// LDS tables, not a correctness input: k_bqsr_count reports any counted quality it has no table slot for and the host retries.
-// `span`: bytes looked at per sampled tile (the exact set after a miss: stride 1, whole tiles)
-__global__ __launch_bounds__(256) void k_qual_present_sample(const uint8_t *__restrict__ qual, uint64_t qual_bytes, uint64_t stride, uint64_t span,
-                                                             unsigned long long *qmask) {
-  const uint64_t ntiles = (qual_bytes + FL_TILE - 1) / FL_TILE;
-  uint32_t m[3] = {0, 0, 0};  // bits 0..95
-  for (uint64_t t = (uint64_t)blockIdx.x * stride; t < ntiles; t += (uint64_t)gridDim.x * stride) {
-    const uint64_t tb = t * FL_TILE, te = (tb + span < qual_bytes) ? tb + span : qual_bytes;
-    for (uint64_t p = tb + (uint64_t)threadIdx.x * 16; p < te; p += 256 * 16) {
-      Chunk ch;
-      ch.load(qual + p);
-      const int nv = (int)((te - p) < 16 ? (te - p) : 16);
-#pragma unroll
-      for (int i = 0; i < 16; i++) {
-        const uint32_t wv = (i >> 2) == 0 ? ch.w0 : ((i >> 2) == 1 ? ch.w1 : ((i >> 2) == 2 ? ch.w2 : ch.w3));
-        const uint32_t q = (wv >> (8 * (i & 3))) & 0xFFu;
-        const uint32_t bit = (i < nv) ? (1u << (q & 31u)) : 0u;
-        const uint32_t wsel = q >> 5;
-        m[0] |= wsel == 0 ? bit : 0u;
-        m[1] |= wsel == 1 ? bit : 0u;
-        m[2] |= wsel == 2 ? bit : 0u;
-      }
-    }
-  }
-  for (int d = 32; d >= 1; d >>= 1) {
-    m[0] |= __shfl_xor(m[0], d, 64);
-    m[1] |= __shfl_xor(m[1], d, 64);
-    m[2] |= __shfl_xor(m[2], d, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    const unsigned long long lo = (unsigned long long)m[0] | ((unsigned long long)m[1] << 32);
-    if (lo) atomicOr(&qmask[0], lo);
-    if (m[2]) atomicOr(&qmask[1], (unsigned long long)m[2]);
-  }
-}
-
-// tile_first[t] = first read r (0 <= r <= n) with qual_off[r] >= t * FL_TILE, for t in [0, ntiles); tile_first[ntiles] = n
-__global__ __launch_bounds__(256) void k_flat_index(const uint64_t *__restrict__ qual_off, uint64_t n_reads, uint64_t ntiles,
-                                                    uint32_t *__restrict__ tile_first) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t > ntiles) return;
-  if (t == ntiles) { tile_first[t] = (uint32_t)n_reads; return; }
-  const uint64_t x = t * FL_TILE;
-  uint64_t lo = 0, hi = n_reads;  // answer in [lo, hi]: qual_off[n_reads] = qual_bytes > x
-  while (lo < hi) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (qual_off[mid] >= x) hi = mid; else lo = mid + 1;
-  }
-  tile_first[t] = (uint32_t)lo;
-}
-
-int ensure_flat_index(elp_ctx *c) {
-  if (c->derived.has_flat_index(c->n, c->qual_bytes)) return 0;
-  const uint64_t ntiles = (c->qual_bytes + FL_TILE - 1) / FL_TILE;
-  ELP_TRY(ensure(c, c->tile_first, ntiles + 2));
-  if (c->n)
-    ELP_LAUNCH(c, "flat_index", k_flat_index, dim3(blocks_for(ntiles + 1, 256)), dim3(256), 0, (const uint64_t *)c->qual_off.p, c->n, ntiles,
-               c->tile_first.p);
-  c->derived.flat_index_n = c->n;
-  c->derived.flat_index_bytes = c->qual_bytes;
-  return 0;
-}
-
-// Do all staged reads have one length?  (every QUAL offset i * len, every SEQ offset SEQ_FRONT + i * ((len + 1) / 2)): then the per-base
-// kernels need no offsets at all (count3.hip).  A fact of the staged columns: checked once per staging, like the tile index.
-__global__ __launch_bounds__(256) void k_uniform_check(uint64_t n, const uint64_t *__restrict__ qual_off, const uint64_t *__restrict__ seq_off,
-                                                       const uint32_t *__restrict__ l_seq, uint64_t len, uint64_t sb, uint64_t seq_front, uint32_t *bad) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool b = false;
-  if (i < n) b = qual_off[i] != i * len || seq_off[i] != seq_front + i * sb || (uint64_t)l_seq[i] != len;
-  if (i == n) b = qual_off[n] != n * len || seq_off[n] != seq_front + n * sb;
-  if (__any(b) && (threadIdx.x & 63) == 0) atomicOr(bad, 1u);
-}
-int ensure_uniform_len(elp_ctx *c) {
-  if (c->derived.has_uniform(c->n, c->qual_bytes)) return 0;
-  c->uniform_len = 0;
-  c->derived.uniform_n = c->n;
-  c->derived.uniform_bytes = c->qual_bytes;
-  if (!c->n || c->qual_bytes % c->n) return 0;
-  const uint64_t len = c->qual_bytes / c->n;
-  if (len == 0 || len > 0x3FFFFFull) return 0;
-  uint32_t *bad = c->err_flag.p + 2;
-  ELP_HIP(c, hipMemsetAsync(bad, 0, 4, c->stream));
-  ELP_LAUNCH(c, "uniform_check", k_uniform_check, dim3(blocks_for(c->n + 1, 256)), dim3(256), 0, c->n, (const uint64_t *)c->qual_off.p,
-             (const uint64_t *)c->seq_off.p, (const uint32_t *)c->l_seq.p, len, (len + 1) / 2, (uint64_t)elp_ctx::SEQ_FRONT, bad);
-  uint32_t hb = 0;
-  ELP_HIP(c, hipMemcpyAsync(&hb, bad, 4, hipMemcpyDeviceToHost, c->stream));
-  ELP_HIP(c, elp::stream_wait(c->stream));
-  ELP_HIP(c, hipMemsetAsync(bad, 0, 4, c->stream));
-  if (!hb) c->uniform_len = (uint32_t)len;
-  return 0;
-}
-
-int adapt_quality_error(elp_ctx *c) {
-  return set_error(c, ELP_ERR_DATA, "Invalid QUAL character (phred > 93) in a duplicate-marking candidate (reference: log.Panic, filters/mark-duplicates.go:64-66)");
-}
-
-// check_quals: report a quality > 93 in a duplicate-marking candidate (computePhredScore panics); the BQSR entry points, which
-// only need the per-read low-quality-tail bounds, pass false and leave that error to a later elp_mark_duplicates
-// the quality-error word of the score kernel, read when somebody needs it (check_quals) - or by elp_mark_duplicates together with its
-// own first read-back (adapt_note): the adapt stage has no synchronisation of its own
-static int adapt_resolve(elp_ctx *c) {
-  if (!c->derived.adapt_pending) return 0;
-  uint32_t w[ADAPT_WORDS];
-  ELP_HIP(c, hipMemcpyAsync(w, c->adapt_err.p, sizeof w, hipMemcpyDeviceToHost, c->stream));
-  ELP_HIP(c, elp::stream_wait(c->stream));
-  adapt_note(c, w);
-  return 0;
-}
-// words: [0] the score kernel's error word, [2 .. 5] the quality values its sampled groups saw (k_score_uniform only)
-void adapt_note(elp_ctx *c, const uint32_t *words) {
-  c->derived.adapt_word_read((words[0] & 1u) != 0);
-  if (c->derived.adapt_sampled) {
-    c->adapt_qmask[0] = (unsigned long long)words[2] | ((unsigned long long)words[3] << 32);
-    c->adapt_qmask[1] = (unsigned long long)words[4] | ((unsigned long long)words[5] << 32);
-  }
-}
-int adapt_begin(elp_ctx *c, int *pos_bits_out) {
-  ELP_HIP(c, hipSetDevice(c->device));
-  const uint64_t n = c->n;
-  ELP_TRY(ensure_flat_index(c));
-  ELP_TRY(ensure(c, c->upos, n + 1));
-  ELP_TRY(ensure(c, c->score, n + 1));
-  ELP_TRY(ensure(c, c->key, n + 1));
-  ELP_TRY(ensure(c, c->qbounds, n + 1));
-  ELP_TRY(ensure(c, c->adapt_err, ADAPT_WORDS + 2));
-  ELP_HIP(c, hipMemsetAsync(c->adapt_err.p, 0, ADAPT_WORDS * sizeof(uint32_t), c->stream));
-  c->derived.adapt_begins();
-  int pos_bits = 1;
-  while (pos_bits < 32 && (c->max_pos >> pos_bits) != 0) pos_bits++;
-  int ref_bits = 1;  // contig codes 0 .. n_ref + 1 (unmapped, then the records that are not sorted at all)
-  while (ref_bits < 32 && (((uint32_t)c->n_ref + 1u) >> ref_bits) != 0) ref_bits++;
-  c->key_bits = ref_bits + pos_bits + 1;
-  *pos_bits_out = pos_bits;
-  return 0;
-}
-// every record's score and low-quality-tail bounds (records without QUAL bytes: zero)
-int adapt_scores(elp_ctx *c) {
-  const uint64_t n = c->n;
-  if (!n) return 0;
-  if (!c->qual_bytes) {  // no QUAL bytes at all: no tile, no kernel
-    ELP_HIP(c, hipMemsetAsync(c->qbounds.p, 0, n * sizeof(uint64_t), c->stream));
-    ELP_HIP(c, hipMemsetAsync(c->score.p, 0, n * sizeof(int32_t), c->stream));
-    return 0;
-  }
-  ELP_TRY(ensure_uniform_len(c));
-  if (c->uniform_len && score_uniform_ok(c->uniform_len) && c->tune.score_kernel != 1) {
-    ELP_TRY(score_uniform(c));  // (writes the score of every record)
-  } else {
-    ELP_HIP(c, hipMemsetAsync(c->score.p, 0, n * sizeof(int32_t), c->stream));  // (a read without bases belongs to no tile's group)
-    const unsigned grid = (unsigned)std::min<uint64_t>(flat_steps<ScoreBody>(c->qual_bytes), (uint64_t)c->n_cu * 4);
-    ELP_LAUNCH(c, "adapt_score_flat", k_score_flat, dim3(grid), dim3(FL_THREADS), 0, n, (const uint64_t *)c->qual_off.p, (const uint8_t *)c->qual.p,
-               c->qual_bytes, (const uint32_t *)c->tile_first.p, (const uint16_t *)c->flag.p, c->score.p, c->qbounds.p, c->adapt_err.p);
-  }
-  c->derived.adapt_pending = true;
-  return 0;
-}
-int ensure_adapted(elp_ctx *c, bool check_quals) {
-  if (c->derived.adapted()) {
-    if (check_quals) ELP_TRY(adapt_resolve(c));
-    return (check_quals && c->derived.adapt_bad_qual) ? adapt_quality_error(c) : 0;
-  }
-  int pos_bits = 1;
-  ELP_TRY(adapt_begin(c, &pos_bits));
-  const uint64_t n = c->n;
-  if (n) {
-    ELP_LAUNCH(c, "adapt_fixed", k_adapt_fixed, dim3(blocks_for(n, 256)), dim3(256), 0, n, (const int32_t *)c->pos.p, (const int32_t *)c->refid.p,
-               (const uint16_t *)c->flag.p, (const uint64_t *)c->cigar_off.p, (const uint32_t *)c->cigar.p, c->upos.p, c->score.p, c->key.p,
-               (uint32_t)c->n_ref, pos_bits, (const uint8_t *)c->has_sr.p);
-    ELP_TRY(adapt_scores(c));
-  }
-  c->derived.keys = c->derived.scores = true;
-  if (check_quals) ELP_TRY(adapt_resolve(c));
-  return (check_quals && c->derived.adapt_bad_qual) ? adapt_quality_error(c) : 0;
-}
-// all the coordinate sort asks for: it reads no score, so nothing elp_bqsr_apply spoils sends it back into the adapt stage
-int ensure_keys(elp_ctx *c) { return c->derived.keys ? 0 : ensure_adapted(c, false); }
-
-// c->qual_present = quality values seen in a sample of the QUAL column (a sizing hint, see k_qual_present_sample)
-int ensure_qual_present(elp_ctx *c, bool exact) {
-  if (c->derived.have_qual_present) return 0;
-  c->qual_present[0] = c->qual_present[1] = 0;
-  // elp_set_tuning "qual_hint" = 1: the hint stays empty, which forces the gather's report-and-retry path (tests)
-  if (!exact && c->tune.qual_hint != 1 && c->derived.scores && c->derived.adapt_sampled) {
-    // the score kernel sampled the column as it went (k_score_uniform): no pass, and no wait of its own if the error word is in already
-    ELP_TRY(adapt_resolve(c));
-    c->qual_present[0] = c->adapt_qmask[0];
-    c->qual_present[1] = c->adapt_qmask[1];
-  } else if (c->qual_bytes && (exact || c->tune.qual_hint != 1)) {
-    unsigned long long *qm;
-    ELP_TRY(scratch(c, 6, 4, &qm));
-    ELP_HIP(c, hipMemsetAsync(qm, 0, 16, c->stream));
-    const uint64_t ntiles = (c->qual_bytes + FL_TILE - 1) / FL_TILE;
-    const uint64_t stride = exact ? 1 : std::min<uint64_t>(16, std::max<uint64_t>(1, ntiles / 2048));
-    const unsigned grid = (unsigned)std::min<uint64_t>((ntiles + stride - 1) / stride, 2048);
-    ELP_LAUNCH(c, "qual_present_sample", k_qual_present_sample, dim3(grid), dim3(256), 0, (const uint8_t *)c->qual.p, c->qual_bytes, stride,
-               (exact || stride == 1) ? FL_TILE : (uint64_t)4096, qm);
-    ELP_HIP(c, hipMemcpyAsync(c->qual_present, qm, 16, hipMemcpyDeviceToHost, c->stream));
-    ELP_HIP(c, elp::stream_wait(c->stream));
-  }
-  // elp_set_tuning "qual_hint_drop" = q removes one quality from the hint (tests: the kernels' no-slot paths)
-  if (!exact && c->tune.qual_hint_drop >= 0) {
-    const int q = c->tune.qual_hint_drop;
-    if (q < 64) c->qual_present[0] &= ~(1ull << q);
-    else if (q < 128) c->qual_present[1] &= ~(1ull << (q - 64));
-  }
-  c->derived.have_qual_present = true;
-  return 0;
-}
 
 // ------------------------------------------------------------------ tie-break
 struct TieCols {
@@ -774,8 +257,8 @@ __global__ __launch_bounds__(256) void k_material_live(uint32_t nu, const uint32
   if (threadIdx.x < elp_ctx::TIE_LIVE_WORDS && acc[threadIdx.x]) atomicOr(&live[threadIdx.x], acc[threadIdx.x]);
 }
 
-// which byte values occur at every live position (bitmap of 256 bits per position, collected in LDS)
-constexpr int TIE_MAX_PACKED = 96;  // live positions up to which the packed keys below are used
+// which byte values occur at every live position (bitmap of 256 bits per position, collected in LDS); TIE_MAX_PACKED (sort_plan.hpp):
+// live positions up to which the packed keys below are used
 struct TiePosList { uint16_t pos[TIE_MAX_PACKED]; uint32_t n; };
 __global__ __launch_bounds__(256) void k_material_values(uint32_t nu, const uint32_t *__restrict__ u_read, TiePosList lp, uint32_t maxq,
                                                          uint32_t *vals /* [n][8] */, TieCols t) {
@@ -891,239 +374,265 @@ __global__ __launch_bounds__(256) void k_large_scatter(uint32_t nu, const uint32
   if (j < nu) perm_out[u_pos[j]] = u_read[vals_sorted[j]];
 }
 
+// ------------------------------------------------------------------ the sort's phases, in the order they run
+// What one sort's phases hand on.  Every size, offset, width and cut comes from sort_plan.hpp.
+struct TieWork {
+  uint64_t n;
+  SortScratch sc;
+  TieScratch lay{0, 0, 0};
+  SortedView sv{nullptr, nullptr, 0};
+  TieCols t{};
+  uint32_t *list = nullptr, *bounds = nullptr;  // the half of `vbuf` the key passes left free; scratch slot 2
+  uint32_t nr = 0, nu = 0, maxq = 0;            // long runs, their members; the longest name
+  uint32_t *u_pos = nullptr, *u_read = nullptr, *u_seg = nullptr, *uv0 = nullptr, *uv1 = nullptr;
+  uint64_t *uk0 = nullptr, *uk1 = nullptr;
+  uint32_t *vcur = nullptr, *vtmp = nullptr;  // the members' order so far and the rounds' second buffer
+  const uint8_t *d_lut = nullptr;
+  explicit TieWork(uint64_t records) : n(records), sc(records) {}
+};
+
+// the key column holds key_bits live bits (adapt packs it): that many digit passes, no histogram read-back; the first pass reads
+// the column itself and numbers the records as it goes (no copy, no index array)
+static int sort_key_passes(elp_ctx *c, uint64_t *presorted, TieWork &w) {
+  const uint64_t n = w.n;
+  uint64_t *kbuf;
+  uint32_t *vbuf;
+  ELP_TRY(scratch(c, 0, w.sc.keys, &kbuf));
+  ELP_TRY(scratch(c, 1, w.sc.vals, &vbuf));
+  ELP_TRY(scratch(c, 2, w.sc.flags, &w.bounds));
+  uint64_t *k0 = kbuf, *k1 = kbuf + n;
+  uint32_t *v0 = vbuf, *v1 = vbuf + n;
+  uint64_t *ks;
+  uint32_t *vs = nullptr;
+  // where key << b | index fits one word (a genome's coordinate key has ~31-34 live bits), the passes move words, not pairs
+  const int idx_bits = index_bits(n);
+  const bool words = sort_words(c->key_bits, idx_bits, c->tune.sort_pairs);
+  if (words && presorted) ks = presorted;
+  else if (words) ELP_TRY(radix_sort_fused(c, c->key.p, n, c->key_bits, idx_bits, k0, k1, &ks));
+  else {
+    ProfScope ps(c, "sort_pairs_");  // (the pair form's passes are booked apart from the word form's: tests see which one ran)
+    ELP_TRY(radix_sort_pairs_low(c, k0, v0, k1, v1, n, key_digits(c->key_bits), &ks, &vs, c->key.p, true));
+  }
+  w.sv = SortedView{ks, vs, words ? (uint32_t)idx_bits : 0u};
+  w.t = TieCols{c->qname_off.p, c->qname.p, c->flag.p, c->mapq.p, c->next_refid.p, c->pnext.p, c->tlen.p};
+  w.list = (vs == v0) ? v1 : v0;  // (sorted words: `vbuf` is free altogether)
+  return 0;
+}
+
+// run members -> compact list; runs up to TIE_SMALL records ranked; bounds of the longer ones -> two short lists in `bounds`
+static int tie_short_runs(elp_ctx *c, TieWork &w) {
+  const uint64_t n = w.n;
+  uint32_t *list_n = c->err_flag.p + 3;  // the scan-total mailbox
+  ELP_HIP(c, hipMemsetAsync(list_n, 0, 4, c->stream));
+  ELP_LAUNCH(c, "tie_scan", k_tie_scan, dim3(blocks_for(n, 256 * TS_TILES)), dim3(256), 0, n, w.sv, c->perm.p, w.list, list_n, w.bounds);
+  // sized for the worst case; workgroups beyond the list's end leave at once
+  ELP_LAUNCH(c, "tie_small", k_tie_small, dim3(blocks_for(n, 256)), dim3(256), 0, n, w.sv, c->perm.p, w.bounds, w.sc.cap, (const uint32_t *)w.list, (const uint32_t *)list_n, w.t);
+  ELP_HIP(c, hipMemsetAsync(list_n, 0, 4, c->stream));
+  return 0;
+}
+
+// ONE read-back: the two counts and the first run bounds (all of them unless there are more than TIE_HEAD runs: then a second copy)
+static int tie_read_bounds(elp_ctx *c, TieWork &w, LongRuns *runs) {
+  const uint32_t head = bounds_head(w.sc.cap);
+  std::vector<uint32_t> hs(w.sc.starts + head), he(head);
+  ELP_HIP(c, hipMemcpyAsync(hs.data(), w.bounds, hs.size() * 4, hipMemcpyDeviceToHost, c->stream));
+  ELP_HIP(c, hipMemcpyAsync(he.data(), w.bounds + w.sc.ends, (size_t)head * 4, hipMemcpyDeviceToHost, c->stream));
+  ELP_HIP(c, elp::stream_wait(c->stream));
+  const uint32_t nr = hs[0];
+  if (!run_counts_ok(hs[0], hs[1], w.sc.cap)) return set_error(c, ELP_ERR_HIP, "coordinate sort: %u starts and %u ends of long runs (internal)", hs[0], hs[1]);
+  std::vector<uint32_t> starts(nr), ends(nr);
+  if (nr > 0 && bounds_in_head(nr)) {
+    std::copy(hs.begin() + w.sc.starts, hs.begin() + w.sc.starts + nr, starts.begin());
+    std::copy(he.begin(), he.begin() + nr, ends.begin());
+  } else if (nr > 0) {
+    ELP_HIP(c, hipMemcpyAsync(starts.data(), w.bounds + w.sc.starts, (size_t)nr * 4, hipMemcpyDeviceToHost, c->stream));
+    ELP_HIP(c, hipMemcpyAsync(ends.data(), w.bounds + w.sc.ends, (size_t)nr * 4, hipMemcpyDeviceToHost, c->stream));
+    ELP_HIP(c, elp::stream_wait(c->stream));
+  }
+  if (!long_runs(std::move(starts), std::move(ends), runs)) return set_error(c, ELP_ERR_HIP, "coordinate sort: long runs overlap (internal)");
+  w.nr = runs->nr;
+  w.nu = runs->nu;
+  return 0;
+}
+
+// The long runs' members, compacted (+ their comparator strings written out, TieScratch::use_rows), and which positions of the string
+// differ at all among them: one kernel, one read-back; the rounds then run over live positions only (no histogram read-back per
+// round, no rounds over constant bytes)
+static int tie_members(elp_ctx *c, TieWork &w, const LongRuns &runs, std::vector<uint16_t> *lp) {
+  const uint32_t nu = w.nu, nr = w.nr, maxq = w.maxq = c->max_qname_len;
+  const TieScratch &lay = w.lay = TieScratch(nu, nr, maxq);  // (m_bytes <= MAX_QNAME + 15: elp_stage enforces the QNAME limit)
+  uint32_t *u;
+  ELP_TRY(scratch(c, 3, lay.words3, &u));
+  w.u_pos = u + lay.u_pos; w.u_read = u + lay.u_read; w.u_seg = u + lay.u_seg; w.uv0 = u + lay.uv0; w.uv1 = u + lay.uv1;
+  uint32_t *d_start = u + lay.d_start, *d_first = u + lay.d_first;
+  uint64_t *uk;
+  ELP_TRY(scratch(c, 4, lay.words4, &uk));
+  w.uk0 = uk + lay.uk0; w.uk1 = uk + lay.uk1;
+  ELP_HIP(c, hipMemcpyAsync(d_start, runs.starts.data(), (size_t)nr * 4, hipMemcpyHostToDevice, c->stream));
+  ELP_HIP(c, hipMemcpyAsync(d_first, runs.first.data(), ((size_t)nr + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  ELP_LAUNCH(c, "large_fill", k_large_fill, dim3(blocks_for(nu, 256)), dim3(256), 0, nu, nr, (const uint32_t *)d_start, (const uint32_t *)d_first, w.sv, w.u_pos, w.u_read, w.u_seg);
+  ELP_LAUNCH(c, "iota", k_iota, dim3(blocks_for(nu, 256)), dim3(256), 0, w.uv0, (uint64_t)nu);
+  static_assert(elp_ctx::MAX_QNAME + 15 <= 32 * elp_ctx::TIE_LIVE_WORDS, "live-position bitmap too small");
+  ELP_TRY(ensure(c, c->tie_live, elp_ctx::TIE_LIVE_WORDS));
+  ELP_HIP(c, hipMemsetAsync(c->tie_live.p, 0, elp_ctx::TIE_LIVE_WORDS * sizeof(uint32_t), c->stream));
+  if (lay.use_rows) {
+    uint8_t *rows = reinterpret_cast<uint8_t *>(u + lay.u_words);
+    ELP_LAUNCH(c, "material_rows", k_material_rows, dim3(blocks_for((uint64_t)nu * (lay.rw >> 3), 256)), dim3(256), 0, nu, (const uint32_t *)w.u_read, maxq, lay.m_bytes, lay.rw,
+               rows, w.t);
+    w.t.rows = rows;
+    w.t.rw = lay.rw;
+  }
+  ELP_LAUNCH(c, "material_live", k_material_live, dim3(blocks_for(nu, 256)), dim3(256), 0, nu, (const uint32_t *)w.u_read, maxq, lay.m_bytes,
+             c->tie_live.p, w.t);
+  uint32_t live[elp_ctx::TIE_LIVE_WORDS];
+  ELP_HIP(c, hipMemcpyAsync(live, c->tie_live.p, sizeof live, hipMemcpyDeviceToHost, c->stream));
+  ELP_HIP(c, elp::stream_wait(c->stream));
+  *lp = live_positions(live, lay.m_bytes);
+  w.vcur = w.uv0;
+  w.vtmp = w.uv1;
+  return 0;
+}
+
+// Few distinct byte values per live position (read names: digits and ':'): the rounds sort on their ranks instead of the bytes, as
+// many positions per 64-bit key as fit - typically two LSD rounds of ~10 passes instead of five rounds of eight.
+static int tie_rank_tables(elp_ctx *c, TieWork &w, const std::vector<uint16_t> &lp, RankFields *f) {
+  TiePosList pl;
+  pl.n = (uint32_t)lp.size();
+  for (size_t k = 0; k < lp.size(); k++) pl.pos[k] = lp[k];
+  uint32_t *s5;
+  ELP_TRY(scratch(c, 5, w.lay.words5, &s5));
+  uint32_t *d_vals = s5 + w.lay.d_vals;
+  uint8_t *d_lut = reinterpret_cast<uint8_t *>(s5 + w.lay.d_lut);
+  ELP_HIP(c, hipMemsetAsync(d_vals, 0, (size_t)pl.n * 8 * 4, c->stream));
+  ELP_LAUNCH(c, "material_values", k_material_values, dim3(std::min(blocks_for(w.nu, 256), 1024u)), dim3(256), 0, w.nu, (const uint32_t *)w.u_read, pl, w.maxq, d_vals, w.t);
+  std::vector<uint32_t> hv((size_t)pl.n * 8);
+  ELP_HIP(c, hipMemcpyAsync(hv.data(), d_vals, hv.size() * 4, hipMemcpyDeviceToHost, c->stream));
+  ELP_HIP(c, elp::stream_wait(c->stream));
+  *f = tie_fields(lp, hv.data());
+  ELP_HIP(c, hipMemcpyAsync(d_lut, f->lut.data(), f->lut.size(), hipMemcpyHostToDevice, c->stream));
+  w.d_lut = d_lut;
+  return 0;
+}
+
+static TiePacked tie_packed(const RankFields &f, FieldCut cut) {
+  TiePacked sel;
+  memset(&sel, 0, sizeof sel);
+  for (int k = cut.lo; k < cut.hi; k++, sel.n++) { sel.pos[sel.n] = f.pos[k]; sel.slot[sel.n] = (uint8_t)f.slot[k]; }
+  field_shifts(f.bits, cut, sel.shift);
+  return sel;
+}
+// one stable round of the members on the low `digits` bytes of the keys in uk0
+static int tie_round_sort(elp_ctx *c, TieWork &w, int digits, uint64_t **ko) {
+  uint32_t *vo;
+  ELP_TRY(radix_sort_pairs_low(c, w.uk0, w.vcur, w.uk1, w.vtmp, w.nu, digits, ko, &vo));
+  if (vo != w.vcur) { w.vtmp = w.vcur; w.vcur = vo; }
+  return 0;
+}
+static int tie_scatter(elp_ctx *c, TieWork &w) {
+  ELP_LAUNCH(c, "large_scatter", k_large_scatter, dim3(blocks_for(w.nu, 256)), dim3(256), 0, w.nu, (const uint32_t *)w.vcur, (const uint32_t *)w.u_pos,
+             (const uint32_t *)w.u_read, c->perm.p);
+  return 0;
+}
+
+// ONE round if everything fits a key, or on the most significant positions that do, with the rest settled by comparison inside the
+// groups of equal keys (k_large_ties); the run id rides in front of the key (no last round on it).  *settled = the permutation is
+// written; else a group of > LT_CAP equal keys was found: the rounds over all positions follow, from the members' first order.
+static int tie_key_round(elp_ctx *c, TieWork &w, const RankFields &f, bool *settled) {
+  const uint32_t nu = w.nu;
+  const int sb = segbits(w.nr);
+  const FieldCut cut = pack_prefix(f.bits, sb);
+  const TiePacked sel = tie_packed(f, cut);
+  ELP_LAUNCH(c, "material_keys", k_material_keys_packed, dim3(blocks_for(nu, 256)), dim3(256), 0, nu, (const uint32_t *)w.vcur, (const uint32_t *)w.u_read,
+             sel, w.d_lut, w.maxq, w.uk0, w.t, (const uint32_t *)(w.nr > 1 ? w.u_seg : nullptr), (uint32_t)cut.total);
+  uint64_t *ko;
+  ELP_TRY(tie_round_sort(c, w, key_digits(sb + cut.total), &ko));
+  *settled = cut.hi == f.n();  // every live position is in the key: equal keys are equal strings, the stable passes kept their order
+  if (*settled) return tie_scatter(c, w);
+  uint32_t *over = c->err_flag.p + 3;  // the scan-total mailbox (zero here)
+  ELP_LAUNCH(c, "large_ties", k_large_ties, dim3(blocks_for(nu, 256)), dim3(256), 0, nu, (const uint64_t *)ko, (const uint32_t *)w.vcur, w.vtmp,
+             (const uint32_t *)w.u_read, w.lay.m_bytes, w.maxq, over, w.t);
+  std::swap(w.vcur, w.vtmp);
+  ELP_TRY(tie_scatter(c, w));
+  uint32_t h_over = 0;
+  ELP_HIP(c, hipMemcpyAsync(&h_over, over, 4, hipMemcpyDeviceToHost, c->stream));
+  ELP_HIP(c, elp::stream_wait(c->stream));
+  *settled = h_over == 0;
+  if (!*settled) {
+    ELP_HIP(c, hipMemsetAsync(over, 0, 4, c->stream));
+    ELP_LAUNCH(c, "iota", k_iota, dim3(blocks_for(nu, 256)), dim3(256), 0, w.uv0, (uint64_t)nu);
+    w.vcur = w.uv0; w.vtmp = w.uv1;
+  }
+  return 0;
+}
+
+// rounds on the ranks from the least significant position upwards, each filling at most 64 bits / 64 positions
+static int tie_packed_rounds(elp_ctx *c, TieWork &w, const RankFields &f) {
+  for (const FieldCut &cut : lsd_cuts(f.bits)) {
+    const TiePacked sel = tie_packed(f, cut);
+    ELP_LAUNCH(c, "material_keys", k_material_keys_packed, dim3(blocks_for(w.nu, 256)), dim3(256), 0, w.nu, (const uint32_t *)w.vcur, (const uint32_t *)w.u_read,
+               sel, w.d_lut, w.maxq, w.uk0, w.t, (const uint32_t *)nullptr, 0u);
+    uint64_t *ko;
+    ELP_TRY(tie_round_sort(c, w, key_digits(cut.total), &ko));
+  }
+  return 0;
+}
+
+// more live positions than the rank keys take (or none at all: no round): rounds on the bytes, least significant positions first
+static int tie_byte_rounds(elp_ctx *c, TieWork &w, const std::vector<uint16_t> &lp) {
+  for (const FieldCut &cut : byte_cuts(lp.size())) {
+    TieSel sel;
+    sel.n = (uint32_t)(cut.hi - cut.lo);
+    for (size_t b = 0; b < 8; b++) sel.pos[b] = b < sel.n ? lp[cut.lo + b] : 0;
+    ELP_LAUNCH(c, "material_keys", k_material_keys_sel, dim3(blocks_for(w.nu, 256)), dim3(256), 0, w.nu, (const uint32_t *)w.vcur,
+               (const uint32_t *)w.u_read, sel, w.maxq, w.uk0, w.t);
+    uint64_t *ko;
+    ELP_TRY(tie_round_sort(c, w, (int)sel.n, &ko));
+  }
+  return 0;
+}
+
+// the last, stable round on the run id keeps the runs apart and in order - with ONE long run (the unmapped block of a file without
+// pile-ups) there is nothing to keep apart
+static int tie_run_id_round(elp_ctx *c, TieWork &w) {
+  if (w.nr > 1) ELP_LAUNCH(c, "seg_keys", k_seg_keys, dim3(blocks_for(w.nu, 256)), dim3(256), 0, w.nu, (const uint32_t *)w.vcur, (const uint32_t *)w.u_seg, w.uk0);
+  if (w.nr > 1) {
+    uint64_t *ko;
+    uint32_t *vo;
+    ELP_TRY(radix_sort_pairs(c, w.uk0, w.vcur, w.uk1, w.vtmp, w.nu, &ko, &vo));
+    if (vo != w.vcur) { w.vtmp = w.vcur; w.vcur = vo; }
+  }
+  return tie_scatter(c, w);
+}
+
+static int tie_long_runs(elp_ctx *c, TieWork &w, const LongRuns &runs) {
+  std::vector<uint16_t> lp;
+  ELP_TRY(tie_members(c, w, runs, &lp));
+  if (rank_keys_apply(lp.size())) {
+    RankFields f;
+    ELP_TRY(tie_rank_tables(c, w, lp, &f));
+    if (key_then_compare(c->tune.tie_rounds, segbits(w.nr), f.bits[0])) {
+      bool settled = false;
+      ELP_TRY(tie_key_round(c, w, f, &settled));
+      if (settled) return 0;
+    }
+    ELP_TRY(tie_packed_rounds(c, w, f));
+  } else {
+    ELP_TRY(tie_byte_rounds(c, w, lp));
+  }
+  return tie_run_id_round(c, w);
+}
+
 static int sort_impl(elp_ctx *c, uint64_t *presorted = nullptr /* the key passes' result, made ahead (sort_presort) */) {
   const uint64_t n = c->n;
   ELP_TRY(ensure_keys(c));
   ELP_TRY(ensure(c, c->perm, n + 1));
   if (n == 0) { c->derived.set_sorted(false); return 0; }
-  uint64_t *kbuf;
-  uint32_t *vbuf, *flags;
-  ELP_TRY(scratch(c, 0, 2 * n + 8, &kbuf));
-  ELP_TRY(scratch(c, 1, 2 * n + 8, &vbuf));
-  ELP_TRY(scratch(c, 2, 2 * n + 8, &flags));
-  uint64_t *k0 = kbuf, *k1 = kbuf + n;
-  uint32_t *v0 = vbuf, *v1 = vbuf + n;
-  // the key column holds key_bits live bits (adapt packs it): that many digit passes, no histogram read-back; the first pass reads
-  // the column itself and numbers the records as it goes (no copy, no index array)
-  uint64_t *ks;
-  uint32_t *vs = nullptr;
-  // where key << b | index fits one word (a genome's coordinate key has ~31-34 live bits), the passes move words, not pairs
-  int idx_bits = 1;
-  while (idx_bits < 32 && (n >> idx_bits) != 0) idx_bits++;
-  const bool words = c->tune.sort_pairs != 1 && c->key_bits >= 1 && c->key_bits + idx_bits <= 64;
-  if (words && presorted) ks = presorted;
-  else if (words) ELP_TRY(radix_sort_fused(c, c->key.p, n, c->key_bits, idx_bits, k0, k1, &ks));
-  else {
-    ProfScope ps(c, "sort_pairs_");  // (the pair form's passes are booked apart from the word form's: tests see which one ran)
-    ELP_TRY(radix_sort_pairs_low(c, k0, v0, k1, v1, n, (c->key_bits + 7) / 8, &ks, &vs, c->key.p, true));
-  }
-  const SortedView sv{ks, vs, words ? (uint32_t)idx_bits : 0u};
-  TieCols t{c->qname_off.p, c->qname.p, c->flag.p, c->mapq.p, c->next_refid.p, c->pnext.p, c->tlen.p};
-  // run members -> compact list (the other half of `vbuf` is free: the radix sort left its result in one half); bounds of the runs
-  // longer than TIE_SMALL -> two short lists in `flags` ([0], [1] their lengths)
-  const uint32_t bounds_cap = (uint32_t)std::min<uint64_t>(n / TIE_SMALL + 16, (2 * n + 8 - 4) / 2);
-  uint32_t *bounds = flags;
-  {
-    uint32_t *list = (vs == v0) ? v1 : v0, *list_n = c->err_flag.p + 3;  // the scan-total mailbox (sorted words: `vbuf` is free altogether)
-    ELP_HIP(c, hipMemsetAsync(list_n, 0, 4, c->stream));
-    ELP_LAUNCH(c, "tie_scan", k_tie_scan, dim3(blocks_for(n, 256 * TS_TILES)), dim3(256), 0, n, sv, c->perm.p, list, list_n, bounds);
-    // sized for the worst case; workgroups beyond the list's end leave at once
-    ELP_LAUNCH(c, "tie_small", k_tie_small, dim3(blocks_for(n, 256)), dim3(256), 0, n, sv, c->perm.p, bounds, bounds_cap, (const uint32_t *)list, (const uint32_t *)list_n, t);
-    ELP_HIP(c, hipMemsetAsync(list_n, 0, 4, c->stream));
-  }
-  // ONE read-back: the two counts and the first run bounds (all of them unless there are more than TIE_HEAD runs: then a second copy)
-  constexpr uint32_t TIE_HEAD = 256;
-  std::vector<uint32_t> hb(4 + 2 * (size_t)TIE_HEAD), starts, ends;
-  {
-    const uint32_t head = std::min<uint32_t>(TIE_HEAD, bounds_cap);
-    ELP_HIP(c, hipMemcpyAsync(hb.data(), bounds, (4 + (size_t)head) * 4, hipMemcpyDeviceToHost, c->stream));
-    ELP_HIP(c, hipMemcpyAsync(hb.data() + 4 + TIE_HEAD, bounds + 4 + bounds_cap, (size_t)head * 4, hipMemcpyDeviceToHost, c->stream));
-    ELP_HIP(c, elp::stream_wait(c->stream));
-  }
-  const uint32_t nr = hb[0];
-  if (nr != hb[1] || nr > bounds_cap) return set_error(c, ELP_ERR_HIP, "coordinate sort: %u starts and %u ends of long runs (internal)", hb[0], hb[1]);
-  uint32_t nu = 0;
-  if (nr > 0) {
-    starts.resize(nr); ends.resize(nr);
-    if (nr <= TIE_HEAD) {
-      std::copy(hb.begin() + 4, hb.begin() + 4 + nr, starts.begin());
-      std::copy(hb.begin() + 4 + TIE_HEAD, hb.begin() + 4 + TIE_HEAD + nr, ends.begin());
-    } else {
-      ELP_HIP(c, hipMemcpyAsync(starts.data(), bounds + 4, (size_t)nr * 4, hipMemcpyDeviceToHost, c->stream));
-      ELP_HIP(c, hipMemcpyAsync(ends.data(), bounds + 4 + bounds_cap, (size_t)nr * 4, hipMemcpyDeviceToHost, c->stream));
-      ELP_HIP(c, elp::stream_wait(c->stream));
-    }
-    std::sort(starts.begin(), starts.end());
-    std::sort(ends.begin(), ends.end());  // runs are disjoint ranges: the r-th start belongs to the r-th end
-    std::vector<uint32_t> first(nr + 1);
-    uint64_t total = 0;
-    for (uint32_t r = 0; r < nr; r++) {
-      if (ends[r] < starts[r] || (r + 1 < nr && starts[r + 1] <= ends[r])) return set_error(c, ELP_ERR_HIP, "coordinate sort: long runs overlap (internal)");
-      first[r] = (uint32_t)total;
-      total += (uint64_t)ends[r] - starts[r] + 1;
-    }
-    first[nr] = (uint32_t)total;
-    nu = (uint32_t)total;
-    // compacted large-run members
-    // (+ the members' comparator strings written out, if that takes at most 512 MB: else every kernel reads the columns)
-    const uint32_t rw = (c->max_qname_len + 15u + 15u) & ~15u;
-    const bool use_rows = (uint64_t)nu * rw <= (512ull << 20);
-    const size_t u_words = ((size_t)5 * nu + 2 * (size_t)nr + 64 + 3) & ~(size_t)3;
-    uint32_t *u;
-    ELP_TRY(scratch(c, 3, u_words + (use_rows ? ((size_t)nu * rw + 64) / 4 : 0), &u));
-    uint32_t *u_pos = u, *u_read = u + nu, *u_seg = u + 2 * (size_t)nu, *uv0 = u + 3 * (size_t)nu, *uv1 = u + 4 * (size_t)nu, *d_start = u + 5 * (size_t)nu,
-             *d_first = d_start + nr;
-    uint64_t *uk;
-    ELP_TRY(scratch(c, 4, (size_t)2 * nu + 16, &uk));
-    uint64_t *uk0 = uk, *uk1 = uk + nu;
-    ELP_HIP(c, hipMemcpyAsync(d_start, starts.data(), (size_t)nr * 4, hipMemcpyHostToDevice, c->stream));
-    ELP_HIP(c, hipMemcpyAsync(d_first, first.data(), ((size_t)nr + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    ELP_LAUNCH(c, "large_fill", k_large_fill, dim3(blocks_for(nu, 256)), dim3(256), 0, nu, nr, (const uint32_t *)d_start, (const uint32_t *)d_first, sv, u_pos, u_read, u_seg);
-    ELP_LAUNCH(c, "iota", k_iota, dim3(blocks_for(nu, 256)), dim3(256), 0, uv0, (uint64_t)nu);
-    const uint32_t maxq = c->max_qname_len;
-    const uint32_t m_bytes = maxq + 15;  // <= MAX_QNAME + 15 <= 32 * TIE_LIVE_WORDS positions (elp_stage enforces the QNAME limit)
-    // which positions of the comparator string differ at all among the members: one kernel, one read-back; the LSD rounds then
-    // take eight live positions each and run every pass (no histogram read-back per round, no rounds over constant bytes)
-    static_assert(elp_ctx::MAX_QNAME + 15 <= 32 * elp_ctx::TIE_LIVE_WORDS, "live-position bitmap too small");
-    ELP_TRY(ensure(c, c->tie_live, elp_ctx::TIE_LIVE_WORDS));
-    ELP_HIP(c, hipMemsetAsync(c->tie_live.p, 0, elp_ctx::TIE_LIVE_WORDS * sizeof(uint32_t), c->stream));
-    if (use_rows) {
-      uint8_t *rows = reinterpret_cast<uint8_t *>(u + u_words);
-      ELP_LAUNCH(c, "material_rows", k_material_rows, dim3(blocks_for((uint64_t)nu * (rw >> 3), 256)), dim3(256), 0, nu, (const uint32_t *)u_read, maxq, m_bytes, rw,
-                 rows, t);
-      t.rows = rows;
-      t.rw = rw;
-    }
-    ELP_LAUNCH(c, "material_live", k_material_live, dim3(blocks_for(nu, 256)), dim3(256), 0, nu, (const uint32_t *)u_read, maxq, m_bytes,
-               c->tie_live.p, t);
-    uint32_t live[elp_ctx::TIE_LIVE_WORDS];
-    ELP_HIP(c, hipMemcpyAsync(live, c->tie_live.p, sizeof live, hipMemcpyDeviceToHost, c->stream));
-    ELP_HIP(c, elp::stream_wait(c->stream));
-    std::vector<uint16_t> lp;
-    for (uint32_t j = 0; j < m_bytes; j++)
-      if ((live[j >> 5] >> (j & 31)) & 1u) lp.push_back((uint16_t)j);
-    uint32_t *vcur = uv0, *vtmp = uv1;
-    bool packed_done = false;
-    if (!lp.empty() && lp.size() <= (size_t)TIE_MAX_PACKED) {
-      // Few distinct byte values per live position (read names: digits and ':'): sort on their ranks instead of the bytes, as
-      // many positions per 64-bit key as fit - typically two LSD rounds of ~10 passes instead of five rounds of eight.
-      TiePosList pl;
-      pl.n = (uint32_t)lp.size();
-      for (size_t k = 0; k < lp.size(); k++) pl.pos[k] = lp[k];
-      uint32_t *d_vals;
-      ELP_TRY(scratch(c, 5, (size_t)TIE_MAX_PACKED * 8 + (size_t)TIE_MAX_PACKED * 64 + 64, &d_vals));
-      uint8_t *d_lut = reinterpret_cast<uint8_t *>(d_vals + TIE_MAX_PACKED * 8);
-      ELP_HIP(c, hipMemsetAsync(d_vals, 0, (size_t)pl.n * 8 * 4, c->stream));
-      ELP_LAUNCH(c, "material_values", k_material_values, dim3(std::min(blocks_for(nu, 256), 1024u)), dim3(256), 0, nu, (const uint32_t *)u_read, pl, maxq, d_vals, t);
-      std::vector<uint32_t> hv((size_t)pl.n * 8);
-      ELP_HIP(c, hipMemcpyAsync(hv.data(), d_vals, hv.size() * 4, hipMemcpyDeviceToHost, c->stream));
-      ELP_HIP(c, elp::stream_wait(c->stream));
-      std::vector<uint8_t> lut((size_t)pl.n * 256, 0);
-      std::vector<int> bits(pl.n);
-      for (uint32_t k = 0; k < pl.n; k++) {
-        int rank = 0;
-        for (int v = 0; v < 256; v++)
-          if ((hv[(size_t)k * 8 + (v >> 5)] >> (v & 31)) & 1u) lut[(size_t)k * 256 + v] = (uint8_t)rank++;
-        int b = 1;
-        while ((1 << b) < rank) b++;
-        bits[k] = b;
-      }
-      ELP_HIP(c, hipMemcpyAsync(d_lut, lut.data(), lut.size(), hipMemcpyHostToDevice, c->stream));
-      // ONE round if everything fits a key, or - round 4 - on the most significant positions that do, with the rest settled by
-      // comparison inside the groups of equal keys (k_large_ties); the run id rides in front of the key (no last round on it)
-      int segbits = 0;
-      while (nr > 1 && (1u << segbits) <= nr) segbits++;  // u_seg = 1 .. nr
-      if (c->tune.tie_rounds != 1 && segbits + bits[0] <= 64) {
-        TiePacked sel;
-        memset(&sel, 0, sizeof sel);
-        int total = 0, hi = 0;
-        while (hi < (int)pl.n && hi < 64 && segbits + total + bits[hi] <= 64) total += bits[hi++];
-        int sh = total;
-        for (int k = 0; k < hi; k++) {
-          sh -= bits[k];
-          sel.pos[sel.n] = pl.pos[k]; sel.shift[sel.n] = (uint8_t)sh; sel.slot[sel.n] = (uint8_t)k;
-          sel.n++;
-        }
-        ELP_LAUNCH(c, "material_keys", k_material_keys_packed, dim3(blocks_for(nu, 256)), dim3(256), 0, nu, (const uint32_t *)vcur, (const uint32_t *)u_read,
-                   sel, (const uint8_t *)d_lut, maxq, uk0, t, (const uint32_t *)(nr > 1 ? u_seg : nullptr), (uint32_t)total);
-        uint64_t *ko;
-        uint32_t *vo;
-        ELP_TRY(radix_sort_pairs_low(c, uk0, vcur, uk1, vtmp, nu, (segbits + total + 7) / 8, &ko, &vo));
-        if (vo != vcur) { vtmp = vcur; vcur = vo; }
-        bool settled = hi == (int)pl.n;  // every live position is in the key: equal keys are equal strings, the stable passes kept their order
-        if (!settled) {
-          uint32_t *over = c->err_flag.p + 3;  // the scan-total mailbox (zero here)
-          ELP_LAUNCH(c, "large_ties", k_large_ties, dim3(blocks_for(nu, 256)), dim3(256), 0, nu, (const uint64_t *)ko, (const uint32_t *)vcur, vtmp,
-                     (const uint32_t *)u_read, m_bytes, maxq, over, t);
-          std::swap(vcur, vtmp);
-          ELP_LAUNCH(c, "large_scatter", k_large_scatter, dim3(blocks_for(nu, 256)), dim3(256), 0, nu, (const uint32_t *)vcur, (const uint32_t *)u_pos,
-                     (const uint32_t *)u_read, c->perm.p);
-          uint32_t h_over = 0;
-          ELP_HIP(c, hipMemcpyAsync(&h_over, over, 4, hipMemcpyDeviceToHost, c->stream));
-          ELP_HIP(c, elp::stream_wait(c->stream));
-          settled = h_over == 0;
-          if (!settled) {  // a group of > LT_CAP equal keys: the rounds over all positions, from the members' first order
-            ELP_HIP(c, hipMemsetAsync(over, 0, 4, c->stream));
-            ELP_LAUNCH(c, "iota", k_iota, dim3(blocks_for(nu, 256)), dim3(256), 0, uv0, (uint64_t)nu);
-            vcur = uv0; vtmp = uv1;
-          }
-        } else {
-          ELP_LAUNCH(c, "large_scatter", k_large_scatter, dim3(blocks_for(nu, 256)), dim3(256), 0, nu, (const uint32_t *)vcur, (const uint32_t *)u_pos,
-                     (const uint32_t *)u_read, c->perm.p);
-        }
-        if (settled) {
-          c->radix_check_pending = true;
-          c->derived.set_sorted(false);
-          return 0;
-        }
-      }
-      // rounds from the least significant position upwards, each filling at most 64 bits / 64 positions
-      for (int hi = (int)pl.n; hi > 0;) {
-        TiePacked sel;
-        memset(&sel, 0, sizeof sel);
-        int total = 0, lo = hi;
-        while (lo > 0 && total + bits[lo - 1] <= 64 && hi - lo < 64) { lo--; total += bits[lo]; }
-        int sh = total;
-        for (int k = lo; k < hi; k++) {
-          sh -= bits[k];
-          sel.pos[sel.n] = pl.pos[k]; sel.shift[sel.n] = (uint8_t)sh; sel.slot[sel.n] = (uint8_t)k;
-          sel.n++;
-        }
-        ELP_LAUNCH(c, "material_keys", k_material_keys_packed, dim3(blocks_for(nu, 256)), dim3(256), 0, nu, (const uint32_t *)vcur, (const uint32_t *)u_read,
-                   sel, (const uint8_t *)d_lut, maxq, uk0, t, (const uint32_t *)nullptr, 0u);
-        uint64_t *ko;
-        uint32_t *vo;
-        ELP_TRY(radix_sort_pairs_low(c, uk0, vcur, uk1, vtmp, nu, (total + 7) / 8, &ko, &vo));
-        if (vo != vcur) { vtmp = vcur; vcur = vo; }
-        hi = lo;
-      }
-      packed_done = true;
-    }
-    for (size_t hi = packed_done ? 0 : lp.size(); hi > 0;) {  // least significant positions first
-      const size_t lo = hi >= 8 ? hi - 8 : 0;
-      TieSel sel;
-      sel.n = (uint32_t)(hi - lo);
-      for (size_t b = 0; b < 8; b++) sel.pos[b] = b < sel.n ? lp[lo + b] : 0;
-      ELP_LAUNCH(c, "material_keys", k_material_keys_sel, dim3(blocks_for(nu, 256)), dim3(256), 0, nu, (const uint32_t *)vcur,
-                 (const uint32_t *)u_read, sel, maxq, uk0, t);
-      uint64_t *ko;
-      uint32_t *vo;
-      ELP_TRY(radix_sort_pairs_low(c, uk0, vcur, uk1, vtmp, nu, (int)sel.n, &ko, &vo));
-      if (vo != vcur) { vtmp = vcur; vcur = vo; }
-      hi = lo;
-    }
-    // the last, stable round on the run id keeps the runs apart and in order - with ONE long run (the unmapped block of a file without
-    // pile-ups) there is nothing to keep apart
-    if (nr > 1) ELP_LAUNCH(c, "seg_keys", k_seg_keys, dim3(blocks_for(nu, 256)), dim3(256), 0, nu, (const uint32_t *)vcur, (const uint32_t *)u_seg, uk0);
-    if (nr > 1) {
-      uint64_t *ko;
-      uint32_t *vo;
-      ELP_TRY(radix_sort_pairs(c, uk0, vcur, uk1, vtmp, nu, &ko, &vo));
-      if (vo != vcur) { vtmp = vcur; vcur = vo; }
-    }
-    ELP_LAUNCH(c, "large_scatter", k_large_scatter, dim3(blocks_for(nu, 256)), dim3(256), 0, nu, (const uint32_t *)vcur, (const uint32_t *)u_pos,
-               (const uint32_t *)u_read, c->perm.p);
-  }
+  TieWork w(n);
+  ELP_TRY(sort_key_passes(c, presorted, w));
+  ELP_TRY(tie_short_runs(c, w));
+  LongRuns runs;
+  ELP_TRY(tie_read_bounds(c, w, &runs));
+  if (runs.nr > 0) ELP_TRY(tie_long_runs(c, w, runs));
   // (a look-back that timed out leaves a wrong permutation: the bit is read by whoever reads the error words next - the following
   // stage, elp_sync, elp_get_permutation, the emit calls: fetch_err - instead of a synchronisation of its own here)
   c->radix_check_pending = true;
@@ -1131,9 +640,6 @@ static int sort_impl(elp_ctx *c, uint64_t *presorted = nullptr /* the key passes
   return 0;
 }
 
-}  // namespace elp
-
-namespace elp {
 // The sort on the context's side lane 1 (common.hpp): the shadow context sees the key column, the comparator's columns and the
 // permutation's buffer as views for the duration of the call, runs on its own stream behind what the context's stream holds now, and
 // before it returns the context's stream is made to wait for whatever the lane still has queued - later stages find the permutation.
@@ -1150,9 +656,8 @@ static int sort_on_side(elp_ctx *c) {
   s->qname_off.p = c->qname_off.p; s->qname.p = c->qname.p; s->has_sr.p = c->has_sr.p;
   s->perm.p = c->perm.p; s->perm.cap = c->perm.cap;
   // the key passes may have been queued ahead (elp_sort_ahead, from inside elp_mark_duplicates): same keys, same length, same lane
-  int ib = 1;
-  while (ib < 32 && (c->n >> ib) != 0) ib++;
-  uint64_t *pre = (c->presort_ks && c->derived.presorted && c->presort_n == c->n && c->presort_idx_bits == ib && c->tune.sort_pairs != 1) ? c->presort_ks : nullptr;
+  const bool pre_ok = c->presort_ks && c->derived.presorted && c->presort_n == c->n && c->presort_idx_bits == index_bits(c->n) && c->tune.sort_pairs != 1;
+  uint64_t *pre = pre_ok ? c->presort_ks : nullptr;
   c->derived.drop_presort();  // (used once: the tie-break leaves its marks in the buffer's other half)
   int rc = sort_impl(s, pre);
   s->key.p = nullptr; s->flag.p = nullptr; s->mapq.p = nullptr; s->next_refid.p = nullptr; s->pnext.p = nullptr; s->tlen.p = nullptr;
@@ -1168,23 +673,20 @@ static int sort_on_side(elp_ctx *c) {
   c->derived.set_sorted(false);
   return 0;
 }
-}  // namespace elp
 
-namespace elp {
 int sort_presort(elp_ctx *c) {
   const uint64_t n = c->n;
   c->derived.drop_presort();
-  if (!c->sort_ahead || n < 2 || !c->derived.keys || c->tune.sort_pairs == 1) return 0;
-  int idx_bits = 1;
-  while (idx_bits < 32 && (n >> idx_bits) != 0) idx_bits++;
-  if (c->key_bits < 1 || c->key_bits + idx_bits > 64) return 0;  // (pairs, not words: the sort makes its passes itself)
+  if (!c->sort_ahead || n < 2 || !c->derived.keys) return 0;
+  const int idx_bits = index_bits(n);
+  if (!sort_words(c->key_bits, idx_bits, c->tune.sort_pairs)) return 0;  // (pairs, not words: the sort makes its passes itself)
   elp_ctx *s = nullptr;
   ELP_TRY(side_lane(c, 1, &s));
   s->n = n; s->key_bits = c->key_bits;
   const int tile_saved = s->tune.radix_tile;
   if (!s->tune.radix_tile) s->tune.radix_tile = c->tune.presort_tile >= 1 && c->tune.presort_tile <= 3 ? c->tune.presort_tile : 2;
   uint64_t *kbuf, *ks = nullptr;
-  int rc = scratch(s, 0, 2 * n + 8, &kbuf);
+  int rc = scratch(s, 0, SortScratch(n).keys, &kbuf);
   if (rc == 0) rc = radix_sort_fused(s, c->key.p, n, c->key_bits, idx_bits, kbuf, kbuf + n, &ks);
   s->tune.radix_tile = tile_saved;
   if (rc != 0) { c->err = s->err; return rc; }

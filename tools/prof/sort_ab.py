@@ -18,7 +18,11 @@ if os.environ.get("ELP_AB_LIB"):
         e.rollback(); e.sync()
         e.mark_duplicates(True, fetch=False); e.sync()   # adapt happens here, outside the timed call
         t0 = time.perf_counter(); e.sort_coordinate(fetch=False); e.sync(); best = min(best, (time.perf_counter() - t0) * 1e3)
-    print(os.path.basename(os.environ["ELP_AB_LIB"]), "sort_coordinate %.3f ms" % best, flush=True)
+    bestq = 1e9
+    for it in range(5):
+        t0 = time.perf_counter(); e.sort_queryname(fetch=False); e.sync(); bestq = min(bestq, (time.perf_counter() - t0) * 1e3)
+    print(os.environ["ELP_AB_LIB"], "sort_coordinate %.3f ms  sort_queryname %.3f ms" % (best, bestq), flush=True)
 else:
     for lib in sys.argv[2:]:
-        subprocess.call([sys.executable, os.path.abspath(__file__), sys.argv[1]], env=dict(os.environ, ELP_AB_LIB=os.path.abspath(lib)))
+        if subprocess.call([sys.executable, os.path.abspath(__file__), sys.argv[1]], env=dict(os.environ, ELP_AB_LIB=os.path.abspath(lib))) != 0:
+            sys.exit(1)  # (nothing more on a device that a run left in doubt)
