@@ -1,10 +1,12 @@
 // bamout.hpp — what the emitters of both output formats share: the columns and staged bytes an output record is gathered from (BamOut),
-// the tag filter's look-up and the choice of the source context in a stream made of two.  bam.hip writes BAM records from them
-// (formatBamAlignment), sam.hip SAM lines (FormatAlignment); emit_stream (bam.hip) is the loop around either pair of kernels.
+// the tag filter's look-up and the choice of the source context in a stream made of two.  bam_out.hip writes BAM records from them
+// (formatBamAlignment), sam.hip SAM lines (FormatAlignment); emit_stream (emit.hip) is the loop around either pair of launches, with the
+// sizes of emit_plan.hpp.
 #pragma once
 
 #include "common.hpp"
 #include "bamtag.hpp"
+#include "emit_plan.hpp"
 
 namespace elp {
 
@@ -65,7 +67,7 @@ __device__ inline uint32_t reg2bin(int32_t beg, int32_t end) {
   return 0;
 }
 // ... of a record with this FLAG whose POS - 1 is beg and whose reference-consuming CIGAR operations add up to ref_span (int32 arithmetic
-// that wraps, as the reference's).  The BAM emitter (bam.hip) and SAM text in (samin.hip) write the bin field with it.
+// that wraps, as the reference's).  The BAM emitter (bam_out.hip) and SAM text in (samin.hip) write the bin field with it.
 __device__ inline uint32_t record_bin(uint16_t flag, int32_t beg, uint32_t ref_span) {
   const int32_t end = (flag & F_UNMAPPED) ? beg : (int32_t)((uint32_t)beg + ref_span - 1u);
   return reg2bin(beg, end);
@@ -83,10 +85,13 @@ struct SamNames {
 // BAM kernels take them)
 int sam_sizes_launch(elp_ctx *c, const BamOut &m, const BamOut &m2, const SamNames &nm, const uint32_t *src, uint64_t k0, uint32_t cnt, uint32_t *sizes, uint32_t *err);
 int sam_emit_launch(elp_ctx *c, const BamOut &m, const BamOut &m2, const SamNames &nm, const uint32_t *src, uint64_t k0, uint32_t cnt, const uint32_t *offs, uint8_t *out);
+// the same two of a BAM chunk (bam_out.hip), under emit_bam_sizes and emit_bam - the split emitters' instantiations (m.sr_on) of either
+// pair under emit_split_*
+int bam_sizes_launch(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint32_t *src, uint64_t k0, uint32_t cnt, uint32_t *sizes, uint32_t *err);
+int bam_emit_launch(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint32_t *src, uint64_t k0, uint32_t cnt, const uint32_t *offs, uint8_t *out);
 
-// bam.hip, for the emitters of other files (split.hip): the chunked size / scan / gather loop over n_out output records, the context's
-// columns as the kernels take them, its reference names and the check that they are set
-enum class OutFormat { BAM, BGZF, SAM };
+// emit.hip, for the emitters of other files (split.hip): the chunked size / scan / gather loop over n_out output records in the format
+// fmt (OutFormat, emit_plan.hpp), the context's columns as the kernels take them, its reference names and the check that they are set
 int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint32_t *src, uint64_t n_out, uint64_t max_raw_rec, uint8_t *out, uint64_t cap,
                 uint64_t *n_bytes_out, OutFormat fmt, const SamNames &nm, const char *who);
 BamOut bam_out_of(const elp_ctx *c);

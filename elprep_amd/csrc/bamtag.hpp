@@ -1,6 +1,6 @@
 // bamtag.hpp — reading a BAM record's bytes on the device: little-endian loads / stores and the optional fields' sizes and integer
-// values (parseBamAlignment, sam/bam-files.go:138-221, 373-396; formatBamTag's integer rule :492-525).  Shared by bam.hip (staging,
-// the emitters) and filter.hip (the predicate that reads optional fields).
+// values (parseBamAlignment, sam/bam-files.go:138-221, 373-396; formatBamTag's integer rule :492-525).  Shared by bam_in.hip (staging),
+// bam_out.hip and sam.hip (the emitters) and filter.hip (the predicate that reads optional fields).
 #pragma once
 
 #include "common.hpp"

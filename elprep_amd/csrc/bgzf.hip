@@ -5,7 +5,7 @@
 //   bgzf_plan.hpp     host arithmetic: the member headers parsed, the pieces cut, the chunks scheduled, the scratch laid out
 //   bgzf_inflate.hip  bgzf_inflate_piece: the blocks of a piece inflated into c->raw, their CRCs checked
 //   bgzf_records.hip  bgzf_scan_piece: where the alignment records start in the inflated bytes
-//   bam.hip           stage_bam_columns: the records into the columns, as elp_stage_bam does
+//   bam_in.hip        stage_bam_columns: the records into the columns, as elp_stage_bam does
 // The writer is bgzf_out.hip.  This function decides nothing about sizes itself.
 #include "bgzf.hpp"
 

@@ -65,9 +65,7 @@ __global__ __launch_bounds__(256) void k_bgzf_frame(const uint8_t *__restrict__ 
   }
 }
 
-uint64_t bgzf_framed_size(uint64_t n_bytes) { return n_bytes + (uint64_t)BGZF_OVERHEAD * ((n_bytes + BGZF_PAYLOAD - 1) / BGZF_PAYLOAD); }
-
-// frames n_bytes of `raw` (device, 16-byte aligned) into `out` (device, bgzf_framed_size(n_bytes) bytes): full blocks are PAYLOAD +
+// frames n_bytes of `raw` (device, 16-byte aligned) into `out` (device, bgzf_framed_size(n_bytes) bytes, bgzf_plan.hpp): full blocks are PAYLOAD +
 // OVERHEAD bytes apart, the last one is short
 int bgzf_frame(elp_ctx *c, const uint8_t *raw, uint64_t n_bytes, uint8_t *out) {
   if (!n_bytes) return 0;

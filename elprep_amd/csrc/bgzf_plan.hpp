@@ -19,7 +19,10 @@ namespace elp {
 struct BgzfBlk { uint64_t in_off; uint32_t in_len, out_len; uint64_t out_off; uint32_t crc; uint32_t pad; };  // CDATA in the piece; ISIZE; place in c->raw
 static_assert(sizeof(BgzfBlk) == 32, "BgzfBlk is four 64-bit words");
 constexpr uint32_t BGZF_PAYLOAD = 65280, BGZF_OVERHEAD = 31;  // bgzf_out.hip: a member's payload at most, the bytes around a stored one
-constexpr uint32_t BGZF_SLOT = 65344;    // bgzf_out.hip: bytes between two slots (>= PAYLOAD + OVERHEAD, a multiple of 64)
+// n_bytes of a stream as BGZF members of stored blocks: the bytes, and BGZF_OVERHEAD around every BGZF_PAYLOAD of them or part of it.
+// The room bgzf_frame and bgzf_deflate (bgzf_out.hip) write into; a compressed member is never larger than its stored form.
+inline uint64_t bgzf_framed_size(uint64_t n_bytes) { return n_bytes + (uint64_t)BGZF_OVERHEAD * ((n_bytes + BGZF_PAYLOAD - 1) / BGZF_PAYLOAD); }
+constexpr uint32_t BGZF_SLOT = 65344;   // bgzf_out.hip: bytes between two slots (>= PAYLOAD + OVERHEAD, a multiple of 64)
 constexpr uint32_t TOK_STRIDE = 21888;   // bgzf_inflate.hip: tokens per block: >= 65536 / 3 + 1, a multiple of 64
 constexpr int RES_THREADS = 1024;        // bgzf_inflate.hip: k_bgzf_resolve's workgroup
 constexpr uint32_t REC_BAD_CAP = 1024;   // bgzf_records.hip: rejected guesses that are listed (more: the repair goes through all blocks)

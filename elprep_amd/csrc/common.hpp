@@ -178,7 +178,7 @@ struct elp_ctx {
   elp_ctx *group_owner = nullptr;            // elp_group_share: the context whose group this one uses ...
   std::vector<elp_ctx *> group_borrowers;    // ... and, at the owner, the contexts that use its group (group_release takes it from them)
 
-  // records staged from BAM bytes (bam.hip): the inflated records stay in HBM, elp_emit_sorted_bam reads bases and tags from them
+  // records staged from BAM bytes (bam_in.hip): the inflated records stay in HBM, elp_emit_sorted_bam reads bases and tags from them
   elp::DVec<uint8_t> raw;
   elp::DVec<uint64_t> raw_off;  // per staged record: offset of its block_size field in raw (n + 1)
   uint64_t raw_n = 0, raw_bytes = 0;
@@ -199,7 +199,7 @@ struct elp_ctx {
   elp::DVec<uint32_t> ref_name_slots;
   uint32_t ref_name_mask = 0;
   bool have_ref_name_table = false;
-  // optional-field settings of a run (bam.hip: elp_set_tag_filter, elp_set_replace_read_group); elp_reset and elp_set_header clear both
+  // optional-field settings of a run (emit.hip: elp_set_tag_filter, elp_set_replace_read_group); elp_reset and elp_set_header clear both
   static constexpr size_t TAG_WORDS = 65536 / 32;
   bool tag_filter = false;             // tag_drop holds a table: bit k of it = fields with the 16-bit key k do not go out
   std::vector<uint32_t> h_tag_drop;    // the host's copy (elp_emit_merged_bam compares the two contexts' tables)
@@ -528,7 +528,7 @@ void group_release(elp_ctx *c);
 int group_sendrecv(elp_ctx *c, int send_peer, const void *send_dev, size_t send_bytes, int recv_peer, void *recv_dev, size_t recv_bytes);  // group.hip
 int tables_written(elp_ctx *c);  // bqsr.hip: dev_tables were just written on c->stream
 int stage_reserve(elp_ctx *c, uint64_t n, uint64_t qb, uint64_t co, uint64_t sb, uint64_t lb);
-// Output record k of a stream made from TWO contexts (bam.hip: elp_emit_merged_*, elp_emit_concat_*): src[k] = rank of the record in the first
+// Output record k of a stream made from TWO contexts (emit.hip: elp_emit_merged_*, elp_emit_concat_*): src[k] = rank of the record in the first
 // context's output, or MERGE_SECOND | its rank in the second's
 constexpr uint32_t MERGE_SECOND = 0x80000000u;
 int keep_concat_src(elp_ctx *groups, uint64_t ng, uint64_t ns, uint32_t *g0_dev, uint32_t *src);  // keep.hip: the unsorted merge's stream as such an array
@@ -542,9 +542,8 @@ inline bool same_replace_rg(const elp_ctx *a, const elp_ctx *b) { return a->repl
 int install_dictionary(elp_ctx *c, int32_t n_ref, const int32_t *ref_len);
 // staging into a context whose dictionary was replaced: its columns hold new refids, the bytes to come the header's
 int staging_refused_after_replace(elp_ctx *c, const char *who);
-int stage_bam_columns(elp_ctx *c, uint32_t n_rec, uint64_t piece_bytes, uint64_t raw_end, uint64_t max_raw_rec, uint16_t split_id);  // bam.hip
-uint64_t bgzf_framed_size(uint64_t n_bytes);                                   // bgzf_out.hip
+int stage_bam_columns(elp_ctx *c, uint32_t n_rec, uint64_t piece_bytes, uint64_t raw_end, uint64_t max_raw_rec, uint16_t split_id);  // bam_in.hip
 int bgzf_frame(elp_ctx *c, const uint8_t *raw, uint64_t n_bytes, uint8_t *out);  // device to device, stored blocks
-int bgzf_deflate(elp_ctx *c, const uint8_t *raw, uint64_t n_bytes, uint8_t *out, uint64_t *out_bytes);  // device to device, compressed members; *out_bytes <= bgzf_framed_size                               // BAM nibbles -> code nibbles on seq4[from, from + bytes)
+int bgzf_deflate(elp_ctx *c, const uint8_t *raw, uint64_t n_bytes, uint8_t *out, uint64_t *out_bytes);  // device to device, compressed members; *out_bytes <= bgzf_framed_size (bgzf_plan.hpp)                               // BAM nibbles -> code nibbles on seq4[from, from + bytes)
 
 }  // namespace elp

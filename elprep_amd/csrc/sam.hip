@@ -1,6 +1,6 @@
 // sam.hip — SAM text out, on the device: FormatAlignment(parseBamAlignment(record)) (sam/sam-files.go:563-598, sam/bam-files.go:317-400)
 // of the records the BAM emitters write, from the same columns and staged bytes (bamout.hpp), in the same chunked loop (emit_stream,
-// bam.hip): a size pass of one thread per record, a scan, an emit pass of one wavefront per record.  The scalar pieces - decimal digits,
+// emit.hip): a size pass of one thread per record, a scan, an emit pass of one wavefront per record.  The scalar pieces - decimal digits,
 // the base table, the float form, a field's text - are samtext.hpp's, which the CPU tests run on the host.
 //
 // The line: QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL separated by tabs, every optional field behind a tab, '\n'.
@@ -26,7 +26,7 @@ namespace st = samtext;
 
 constexpr uint32_t SR_TEXT_LEN = 7;  // "\tsr:i:1"
 // text size of output record k; the error bits of the BAM size pass (2 malformed fields, 16 an H field) and 32: a refid outside the names
-// SR (the split emitters, split.hip), set_sr: as out_size's (bam.hip) - the tagged copy's first sr field goes out as "\tsr:i:1", a copy
+// SR (the split emitters, split.hip), set_sr: as out_size's (bam_out.hip) - the tagged copy's first sr field goes out as "\tsr:i:1", a copy
 // without one gets it behind its last field
 template <bool OPT, bool SR = false>
 __device__ inline uint32_t sam_out_size(const BamOut &m, const SamNames &nm, uint32_t i, uint32_t *err, bool set_sr = false) {
@@ -48,7 +48,7 @@ __device__ inline uint32_t sam_out_size(const BamOut &m, const SamNames &nm, uin
   if (c0 == c1) size += 1;
   for (uint64_t k = c0; k < c1; k++) size += st::u32_width(m.cigar[k] >> 4) + 1u;
   size += 2u * m.l_seq[i];  // (the column, as the emit pass reads it; equal to the staged field)
-  // the optional fields: out_size's walk (bam.hip), counting text
+  // the optional fields: out_size's walk (bam_out.hip), counting text
   const uint8_t *t = rec + fixed;
   bool rg_seen = false, sr_seen = false;
   while (t + 3 <= end) {

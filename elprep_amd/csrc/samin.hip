@@ -1,6 +1,6 @@
 // samin.hip — SAM text IN on the device (elp_stage_sam): parseSamAlignment (sam/sam-files.go:386-410) + AddREFID
 // (filters/simple-filters.go:208-231) + formatBamAlignment (sam/bam-files.go:635-737) as kernels.  Every alignment line becomes the BAM
-// record the reference would write for it, in c->raw with its offset in c->raw_off; stage_bam_columns (bam.hip) then cuts the records
+// record the reference would write for it, in c->raw with its offset in c->raw_off; stage_bam_columns (bam_in.hip) then cuts the records
 // into the columns as it does for elp_stage_bam and elp_stage_bgzf - whatever reads staged records reads these.
 //
 // Per piece of text (whole lines, at most PIECE bytes):

@@ -15,11 +15,11 @@
 //       as keep.hip's by_split order) sorts by the key's one or two bytes, and one thread per file finds its first entry in the sorted keys
 //       by binary search (as keep.hip's k_keep_split0_end; up to 65535 files: too many counters for LDS).  The n_files + 1 bounds are the
 //       one read-back.
-//   (2) emit_stream (bam.hip) once per file on that file's slice of the list, with the emitters' SR instantiation (BamOut.sr_on): bit 31 of
+//   (2) emit_stream (emit.hip) once per file on that file's slice of the list, with the emitters' SR instantiation (BamOut.sr_on): bit 31 of
 //       an entry makes the walk over the optional fields write SmallMap.Set(sr, int64(1)).  BGZF members, carried bytes and device passes
 //       are emit_stream's, per file: nothing crosses a file boundary.
-// Scratch: slots 2 (entries), 3 (keys) and 6 (bounds, group table) - emit_stream and bgzf_deflate use 0, 1, 4, 5 and 7.  Nothing of the
-// context's derived state is read or written (csrc/derived.hpp), not the split-id column and not the permutation.
+// Scratch: slots 2 (entries), 3 (keys) and 6 (bounds, group table), beside emit_stream's and bgzf_deflate's - who holds which slot from
+// when to when: emit_plan.hpp.  Nothing of the context's derived state is read or written (csrc/derived.hpp), not the split-id column and not the permutation.
 #include <vector>
 
 #include "common.hpp"

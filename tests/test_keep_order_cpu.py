@@ -36,7 +36,7 @@ def test_the_new_entry_points_reject_null_contexts_without_a_gpu():
 
 
 def test_the_no_permutation_messages_name_the_third_call():
-    for src in ("ctx.hip", "bam.hip"):
+    for src in ("ctx.hip", "emit.hip"):
         text = open(os.path.join(ROOT, "elprep_amd", "csrc", src)).read()
         assert "or elp_sort_queryname first" not in text
         assert "elp_sort_coordinate, elp_sort_queryname or elp_order_keep first" in text
