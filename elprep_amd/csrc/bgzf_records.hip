@@ -168,6 +168,14 @@ __global__ void k_rec_tail(const uint64_t *__restrict__ entry, const uint64_t *_
   out[0] = e;
 }
 
+// what the decoder reported for the inflate piece, from the result words as read back (once per inflate piece)
+static int inflate_verdict(elp_ctx *c, BgzfPiece &piece, const BgzfRes &hr) {
+  if (hr.inflate & INFLATE_BAD_DATA) return set_error(c, ELP_ERR_DATA, "elp_stage_bgzf: a block does not inflate (corrupt DEFLATE data or wrong ISIZE)");
+  if (hr.inflate & INFLATE_BAD_CRC) return set_error(c, ELP_ERR_DATA, "invalid CRC-32 value for a data block in a BGZF file");
+  piece.inflate_checked = true;
+  return 0;
+}
+
 // One scan piece: the records that start in the blocks [rel, rel + nb) of the inflate piece, the first of them at `begin` in c->raw.
 // Guess, walk, check, (read-back: also what the decoder reported, once per inflate piece,) repair where a guess was rejected, the scan of
 // the counts, the starts into c->raw_off behind the c->n that are there, the end of the last complete record.
@@ -180,17 +188,24 @@ int bgzf_scan_piece(elp_ctx *c, BgzfPiece &piece, size_t rel, uint32_t nb, uint6
   ELP_HIP(c, hipMemsetAsync(res, 0, BgzfRes::CLEAR_SCAN, st));
   const BgzfBlk &last = piece.tb[rel + nb - 1];
   const uint64_t end = last.out_off + last.out_len;
+  // a piece wholly in front of the first record (a header prefix longer than a scan piece) stages nothing and `begin` stands; its blocks
+  // are inflated and checked all the same
+  const bool in_front = end <= begin;
   const RecScan rs{c->raw.p, begin, end, c->n_ref};
-  ELP_LAUNCH(c, "stage_bgzf_guess", k_rec_guess, dim3(nb), dim3(256), 0, rs, d_blk, entry, c->tune.bgzf_weak_guess);
-  ELP_LAUNCH(c, "stage_bgzf_walk", k_rec_walk, dim3(blocks_for(nb, 64)), dim3(64), 0, rs, d_blk, nb, (const uint64_t *)entry, exit_, cnt);
-  ELP_LAUNCH(c, "stage_bgzf_check", k_rec_check, dim3(blocks_for(nb, 256)), dim3(256), 0, rs, d_blk, nb, (const uint64_t *)entry, (const uint64_t *)exit_, &res->bad, piece.bad_list);
-  BgzfRes hr;
-  ELP_HIP(c, hipMemcpyAsync(&hr, res, sizeof hr, hipMemcpyDeviceToHost, st));
-  ELP_HIP(c, elp::stream_wait(st));
-  if (!piece.inflate_checked) {
-    if (hr.inflate & INFLATE_BAD_DATA) return set_error(c, ELP_ERR_DATA, "elp_stage_bgzf: a block does not inflate (corrupt DEFLATE data or wrong ISIZE)");
-    if (hr.inflate & INFLATE_BAD_CRC) return set_error(c, ELP_ERR_DATA, "invalid CRC-32 value for a data block in a BGZF file");
-    piece.inflate_checked = true;
+  if (!in_front) {
+    ELP_LAUNCH(c, "stage_bgzf_guess", k_rec_guess, dim3(nb), dim3(256), 0, rs, d_blk, entry, c->tune.bgzf_weak_guess);
+    ELP_LAUNCH(c, "stage_bgzf_walk", k_rec_walk, dim3(blocks_for(nb, 64)), dim3(64), 0, rs, d_blk, nb, (const uint64_t *)entry, exit_, cnt);
+    ELP_LAUNCH(c, "stage_bgzf_check", k_rec_check, dim3(blocks_for(nb, 256)), dim3(256), 0, rs, d_blk, nb, (const uint64_t *)entry, (const uint64_t *)exit_, &res->bad, piece.bad_list);
+  }
+  BgzfRes hr{};
+  if (!in_front || !piece.inflate_checked) {
+    ELP_HIP(c, hipMemcpyAsync(&hr, res, sizeof hr, hipMemcpyDeviceToHost, st));
+    ELP_HIP(c, elp::stream_wait(st));
+  }
+  if (!piece.inflate_checked) ELP_TRY(inflate_verdict(c, piece, hr));
+  if (in_front) {
+    *out = BgzfScan{0, begin, 0};
+    return 0;
   }
   if (hr.bad) ELP_LAUNCH(c, "stage_bgzf_repair", k_rec_repair, dim3(1), dim3(1), 0, rs, d_blk, nb, entry, exit_, cnt, (const uint32_t *)&res->bad, piece.bad_list);
   uint32_t n_rec = 0;
