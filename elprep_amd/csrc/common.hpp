@@ -303,6 +303,34 @@ struct elp_ctx {
 
 namespace elp {
 
+// The columns a side lane's shadow context borrows from its context for the duration of a call: view() makes the shadow's DVec point at
+// the context's buffer, and the destructor takes every view back (p = nullptr, cap = 0) whichever way the call ends.  DVec's destructor
+// and release() free whatever p holds, so a view left standing would free the context's column together with the shadow.
+// A view carries cap 0: the shadow does not own the buffer and must not grow it.  ensure() on a view finds n > cap, allocates, and then
+// hipFrees the old p - the CONTEXT's column, under the context's live pointer; the buffer it leaves in the shadow is dropped unfreed by
+// the destructor here.  Nothing that runs on a lane calls ensure on a borrowed column, with one exception that `with_cap` makes
+// explicit: the sorts ensure the permutation buffer to n + 1 elements themselves, so it is lent with the context's capacity (their
+// callers ensure it on the context first) and that call finds nothing to do.
+class LaneViews {
+  struct Item { void *vec; void (*take_back)(void *); };
+  std::vector<Item> items;
+
+ public:
+  template <class... Col>
+  LaneViews(elp_ctx *shadow, elp_ctx *ctx, Col... cols) { (view(shadow->*cols, ctx->*cols), ...); }  // cols: &elp_ctx::flag, ...
+  LaneViews(const LaneViews &) = delete;
+  LaneViews &operator=(const LaneViews &) = delete;
+  ~LaneViews() {
+    for (const Item &it : items) it.take_back(it.vec);
+  }
+  template <class T>
+  void view(DVec<T> &to, const DVec<T> &from, bool with_cap = false) {
+    to.p = from.p;
+    to.cap = with_cap ? from.cap : 0;
+    items.push_back(Item{&to, [](void *v) { DVec<T> *d = static_cast<DVec<T> *>(v); d->p = nullptr; d->cap = 0; }});
+  }
+};
+
 int set_error(elp_ctx *c, int code, const char *fmt, ...);
 int prof_begin(elp_ctx *c, const char *name);  // returns pending index or -1
 void prof_end(elp_ctx *c, int pending);

@@ -150,11 +150,12 @@ static int order_keep(elp_ctx *c, bool by_split) {
   elp_ctx *s = nullptr;
   ELP_TRY(side_lane(c, 1, &s));
   s->n = c->n; s->n_sr = c->n_sr; s->max_split = c->max_split;
-  s->has_sr.p = c->has_sr.p; s->split.p = c->split.p;
-  s->perm.p = c->perm.p; s->perm.cap = c->perm.cap;
-  int rc = keep_impl(s, by_split && c->max_split != 0);
-  s->has_sr.p = nullptr; s->split.p = nullptr;
-  s->perm.p = nullptr; s->perm.cap = 0;
+  int rc;
+  {
+    LaneViews views(s, c, &elp_ctx::has_sr, &elp_ctx::split);
+    views.view(s->perm, c->perm, true);
+    rc = keep_impl(s, by_split && c->max_split != 0);
+  }
   if (rc == 0) rc = radix_check(s);  // (the lane's own error words: a look-back timeout of the radix passes is read here)
   if (rc == 0 && elp::stream_wait(s->stream) != hipSuccess) rc = set_error(s, ELP_ERR_HIP, "elp_order_keep: the sort lane's stream failed");
   if (rc != 0) {

@@ -14,6 +14,8 @@
 // of (set, RG, strand, tile), every member compares itself with the members behind it in its bucket (the all-pairs test of
 // fillGraphFromAGroup, :232-243, per (RG, tile) bucket) and joins them in a lock-free union-find; optical = members - components.
 #include "common.hpp"
+#include "metrics_plan.hpp"
+#include "optical_name.hpp"
 
 namespace elp {
 
@@ -34,8 +36,6 @@ struct MxCols {
   const uint16_t *split;
   int32_t n_split;  // 1 + largest staged split id
 };
-constexpr uint32_t OPT_SMALL = 32;        // sets up to this size: one thread, all pairs
-constexpr uint32_t OPT_LIST_CAP = 300000; // :289-299
 
 __device__ __forceinline__ uint32_t lib_row(const MxCols &m, uint32_t i) {
   const uint16_t rg = m.rgid[i];
@@ -52,6 +52,12 @@ __device__ __forceinline__ void order_ends(const MxCols &m, uint32_t second, uin
   const bool v1 = m.flag[a1] & F_REVERSED, v2 = m.flag[a2] & F_REVERSED;
   if (r1 > r2 || (r1 == r2 && (p1 > p2 || (p1 == p2 && v1 && !v2)))) { uint32_t t = a1; a1 = a2; a2 = t; }
 }
+// library row of a pair group's origin (origin.aln1.LIBID() :381); `mate` = m.mate[owner]
+__device__ __forceinline__ uint32_t origin_lib(const MxCols &m, uint32_t owner, uint32_t mate) {
+  uint32_t a1, a2;
+  order_ends(m, owner, mate, a1, a2);
+  return lib_row(m, a1);
+}
 __device__ __forceinline__ uint32_t listed_read(const MxCols &m, uint32_t owner) {  // :216-221 / :278-283
   uint32_t a1, a2;
   order_ends(m, owner, m.mate[owner], a1, a2);
@@ -65,7 +71,7 @@ __device__ __forceinline__ uint32_t listed_read(const MxCols &m, uint32_t owner)
 // so everything behind this kernel works on a compact list instead of record-indexed arrays.  A workgroup owns a contiguous range
 // of records, collects its losers in LDS and appends them with one global atomic per ~DC_CAP entries (a global atomic per wave
 // on the one list counter would serialise at ~12 ns each).
-constexpr int DC_CAP = 2048, DC_STEP = 1024;
+// (DC_CAP, DC_STEP: metrics_plan.hpp)
 // one LDS atomic per distinct counter of the wave (nearly all records of a wave add to the same one or two cells: 64 lanes on one
 // LDS address would serialise)
 __device__ __forceinline__ void wave_count(unsigned int *lds, int cell) {
@@ -185,54 +191,7 @@ __global__ __launch_bounds__(256) void k_opt_starts(uint32_t L, const uint32_t *
   if (j == L - 1) gstart[G] = L;
 }
 
-struct Tile { long long t, x, y; };
-
-// computeTileInfo :50-71; *bad is set where internal.ParseInt would panic (strconv.ParseInt(s, 10, 64): one optional sign, one or
-// more ASCII digits - leading zeros of any length -, the value in [-2^63, 2^63 - 1]).  One pass over the name, eight bytes per load: the
-// integer value (and parse status) of fields 2..6 is kept in scalars, the field count decides at the end which three are used
-// (7 fields -> 4,5,6; 5 fields -> 2,3,4).
-// `word(k)` = bytes 8 k .. 8 k + 7 of the name
-template <class W>
-__device__ __forceinline__ Tile tile_parse(uint32_t len, bool *bad, W word) {
-  long long v2 = 0, v3 = 0, v4 = 0, v5 = 0, v6 = 0;
-  uint32_t badmask = 0;       // bit k: field k does not parse
-  int col = 0;
-  unsigned long long x = 0;   // magnitude of the current field
-  uint32_t ndig = 0;          // digits seen in the current field
-  bool neg = false, fbad = false, first = true;
-  uint64_t w = 0;
-  for (uint32_t i = 0;; i++) {
-    const bool end = i == len;
-    if (!end && (i & 7u) == 0) w = word(i >> 3);
-    const uint32_t ch = end ? (uint32_t)':' : (uint32_t)(w >> (8 * (i & 7u))) & 0xFFu;
-    if (ch == ':') {
-      const bool fb = fbad || ndig == 0 || x > (neg ? 0x8000000000000000ull : 0x7FFFFFFFFFFFFFFFull);
-      const long long val = (long long)(neg ? 0ull - x : x);
-      if (col == 2) v2 = val; else if (col == 3) v3 = val; else if (col == 4) v4 = val; else if (col == 5) v5 = val; else if (col == 6) v6 = val;
-      if (col >= 2 && col <= 6 && fb) badmask |= 1u << col;
-      col++;
-      x = 0; ndig = 0; neg = false; fbad = false; first = true;
-    } else {
-      if (first && (ch == '+' || ch == '-')) {
-        neg = ch == '-';
-      } else {
-        const uint32_t d = ch - (uint32_t)'0';
-        if (d > 9) fbad = true;
-        else if (x > 922337203685477580ull) fbad = true;  // over 2^63 already (x * 10 >= 9223372036854775810); stays bad
-        else x = x * 10 + d;
-        ndig++;
-      }
-      first = false;
-    }
-    if (end) break;
-  }
-  int a;
-  if (col == 7) a = 4;
-  else if (col == 5) a = 2;
-  else return Tile{-1, -1, -1};
-  if (badmask & (7u << a)) { *bad = true; return Tile{-1, -1, -1}; }
-  return a == 4 ? Tile{v4, v5, v6} : Tile{v2, v3, v4};
-}
+// Tile, tile_parse, Member, go_abs_diff, optical_close: optical_name.hpp
 // Names of up to 48 bytes (all of a sequencer's) are fetched with six loads issued together, in front of the parse: the members of the
 // duplicate sets are scattered over the name pool, and a load per eight parsed bytes brought the name's cache line in again and again
 // (850 B of HBM traffic per member, measured; a resident wave per name holds more lines than the caches do).
@@ -244,10 +203,6 @@ __device__ inline Tile tile_info(const uint8_t *__restrict__ q, uint32_t len, bo
   }
   return tile_parse(len, bad, [&](uint32_t k) { return load8(q + 8 * k); });
 }
-
-// rg_rev = rgid << 1 | reversed; bad: the name does not parse (the reference panics if it parses it: a member of a strand list of
-// 2..OPT_LIST_CAP entries, :327-368; k_opt_eval decides)
-struct Member { long long t, x, y; uint32_t rg_rev, bad; };
 
 __device__ inline Member make_member(const MxCols &m, uint32_t read) {
   bool bad = false;
@@ -290,15 +245,13 @@ __device__ inline uint32_t uf_find(uint32_t *p, uint32_t x) {
   while (p[x] != r) { uint32_t nx = p[x]; p[x] = r; x = nx; }
   return r;
 }
-// absInt (filters/utils.go:62) of a - b on Go's int: the difference wraps, and absInt(MinInt64) stays MinInt64 (so it is "close")
-__device__ __forceinline__ long long go_abs_diff(long long a, long long b) {
-  const unsigned long long d = (unsigned long long)a - (unsigned long long)b;
-  return (long long)((long long)d < 0 ? 0ull - d : d);
+// incrementDuplicatesCountsHistograms :150-174 for a set of cnt listed reads, `optical` of them optical duplicates: idx[k] is the
+// index histogram k counts at - cnt, cnt - optical, optical + 1 (if optical > 0) -, nothing where it is <= 0 (cnt - optical >= 1: a set
+// has a component); hist_bin: indices beyond the last bin count into the last bin
+__device__ __forceinline__ void hist_idx(uint32_t cnt, uint32_t optical, int idx[3]) {
+  idx[0] = (int)cnt; idx[1] = (int)(cnt - optical); idx[2] = optical ? (int)optical + 1 : 0;
 }
-__device__ __forceinline__ bool optical_close(const Member &a, const Member &b, long long dist) {  // isOpticalDuplicate + same RG / strand list / tile
-  if (a.t == -1 || b.rg_rev != a.rg_rev || b.t != a.t) return false;
-  return go_abs_diff(a.x, b.x) <= dist && go_abs_diff(a.y, b.y) <= dist;
-}
+__device__ __forceinline__ int hist_bin(int idx, int hist_len) { return idx < hist_len ? idx : hist_len - 1; }
 
 // one thread per member slot; the origin's slot evaluates its set: optical count = n - #components under the closeness relation
 // (sets of two and three members, the bulk, are evaluated in registers; larger ones with a union-find in `parent`)
@@ -306,7 +259,7 @@ __device__ __forceinline__ bool optical_close(const Member &a, const Member &b, 
 // :150-174: sets of n listed reads, of them `optical` optical duplicates - bin n of the first, bin n - optical (if > 0) of the
 // second, bin optical + 1 (if optical > 0) of the third; indices beyond the last bin count into the last bin); the first lds_bins
 // bins of every histogram are collected in LDS like the optical counts
-__global__ __launch_bounds__(128) void k_opt_eval(MxCols m, uint32_t total, const uint2 *__restrict__ ginfo, const Member *__restrict__ members,
+__global__ __launch_bounds__(MX_EVAL_THREADS) void k_opt_eval(MxCols m, uint32_t total, const uint2 *__restrict__ ginfo, const Member *__restrict__ members,
                                                   uint32_t *__restrict__ parent, long long dist, unsigned long long *__restrict__ ctr,
                                                   uint32_t *err, unsigned long long *__restrict__ hist, int hist_len, int lds_bins,
                                                   uint32_t *__restrict__ linfo, uint32_t *__restrict__ lcount, uint32_t *n_large) {
@@ -345,6 +298,7 @@ __global__ __launch_bounds__(128) void k_opt_eval(MxCols m, uint32_t total, cons
   } else if (cnt >= 2) {
   const Member *g = members + b;
   {  // lists of up to OPT_SMALL entries: a bad name in a list of two or more is the reference's panic (:327-368)
+    // (the strand tally a second time, not a helper of the two: either form of one changed this kernel's instructions)
     uint32_t nr = 0, bad_f = 0, bad_r = 0;
     for (uint32_t k = 0; k < cnt; k++) {
       const uint32_t rev = g[k].rg_rev & 1u, bad = g[k].bad;
@@ -380,16 +334,15 @@ __global__ __launch_bounds__(128) void k_opt_eval(MxCols m, uint32_t total, cons
   }
   if (!large && (optical || (hist && cnt >= 2))) {
     const uint32_t owner = gi.y;
-    uint32_t a1, a2;
-    order_ends(m, owner, m.mate[owner], a1, a2);
-    const uint32_t lib = lib_row(m, a1);  // origin.aln1.LIBID() :381
+    const uint32_t lib = origin_lib(m, owner, m.mate[owner]);
     if (optical) atomicAdd(&lds_opt[lib], optical);
     if (hist && cnt >= 2) {
-      const int idx[3] = {(int)cnt, (int)(cnt - optical), optical ? (int)optical + 1 : 0};  // cnt - optical >= 1: a set has a component
+      int idx[3];
+      hist_idx(cnt, optical, idx);
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         if (idx[k] <= 0) continue;
-        const int bin = idx[k] < hist_len ? idx[k] : hist_len - 1;
+        const int bin = hist_bin(idx[k], hist_len);
         if (bin < lds_bins) atomicAdd(&lds_h[((int)lib * 3 + k) * lds_bins + bin], 1u);
         else atomicAdd(&hist[((size_t)lib * 3 + k) * hist_len + bin], 1ull);
       }
@@ -466,16 +419,14 @@ __global__ __launch_bounds__(256) void k_large_final(MxCols m, uint32_t total, c
   const unsigned long long sc = setcnt[b];
   const uint32_t optical = (uint32_t)sc - (uint32_t)(sc >> 32);
   const uint32_t owner = ginfo[b].y;
-  uint32_t a1, a2;
-  order_ends(m, owner, m.mate[owner], a1, a2);
-  const uint32_t lib = lib_row(m, a1);
+  const uint32_t lib = origin_lib(m, owner, m.mate[owner]);
   if (optical) atomicAdd(&ctr[lib * ELP_NCTR + 6], (unsigned long long)optical);
   if (hist) {
-    const uint32_t cnt = lcount[b];
-    const int idx[3] = {(int)cnt, (int)(cnt - optical), optical ? (int)optical + 1 : 0};
+    int idx[3];
+    hist_idx(lcount[b], optical, idx);
     for (int k = 0; k < 3; k++) {
       if (idx[k] <= 0) continue;
-      const int bin = idx[k] < hist_len ? idx[k] : hist_len - 1;
+      const int bin = hist_bin(idx[k], hist_len);
       atomicAdd(&hist[((size_t)lib * 3 + k) * hist_len + bin], 1ull);
     }
   }
@@ -493,7 +444,7 @@ __global__ __launch_bounds__(256) void k_origin_count(MxCols m, unsigned long lo
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m.n; i += (uint64_t)gridDim.x * blockDim.x) {
     const uint32_t mt = m.mate[i];
     if (mt == EMPTY || mt > (uint32_t)i || m.pair_win[i] != EMPTY) continue;  // not the owner of a pair, or of a pair that lost
-    uint32_t a1, a2;
+    uint32_t a1, a2;  // (origin_lib, written out: through the helper this kernel's instructions changed)
     order_ends(m, (uint32_t)i, mt, a1, a2);
     atomicAdd(&lds_org[lib_row(m, a1)], 1u);
   }
@@ -502,146 +453,167 @@ __global__ __launch_bounds__(256) void k_origin_count(MxCols m, unsigned long lo
     if (lds_org[k]) atomicAdd(&origins[k], (unsigned long long)lds_org[k]);
 }
 
-static int metrics_impl(elp_ctx *c, int dist, int64_t *counters_host, int64_t *hist_host, int hist_len) {
-  const uint64_t n = c->n;
-  const int ncell = (c->n_lib + 1) * ELP_NCTR;
-  if (!c->derived.marked) return set_error(c, ELP_ERR_ARG, "elp_dup_metrics: call elp_mark_duplicates first");
-  // device block: the counters, then (if asked for) the origins per library and the three histograms per library
-  const size_t nhist = hist_host ? (size_t)(c->n_lib + 1) * 3 * (size_t)hist_len : 0, norg = hist_host ? (size_t)(c->n_lib + 1) : 0;
-  const int n_split = (int)c->max_split + 1;
-  const size_t npr = (size_t)n_split * (size_t)(c->n_lib + 1);
-  if (((size_t)ncell + npr) * sizeof(unsigned int) > 46000)  // + 16 KB of static LDS in k_dup_counters
-    return set_error(c, ELP_ERR_UNSUPPORTED, "elp_dup_metrics: %d split ids x %d libraries in one context", n_split, c->n_lib + 1);
-  unsigned long long *ctr;
-  ELP_TRY(scratch(c, 0, (size_t)ncell + norg + nhist + npr + 8, &ctr));
-  unsigned long long *origins = ctr + ncell, *hist = hist_host ? origins + norg : nullptr, *pair_reads = ctr + ncell + norg + nhist;
-  hipStream_t st = c->stream;
-  ELP_HIP(c, hipMemsetAsync(ctr, 0, ((size_t)ncell + norg + nhist + npr) * sizeof(unsigned long long), st));
-  int lds_bins = hist_host ? std::min(hist_len, 32) : 0;
-  if ((size_t)(c->n_lib + 1) * (1 + 3 * (size_t)lds_bins) * sizeof(unsigned int) > 32768) lds_bins = 0;
-  if (n) {
-    MxCols m{n, c->refid.p, c->flag.p, c->rgid.p, c->rg_lib.p, c->upos.p, c->qname_off.p, c->qname.p, c->mate.p, c->pair_win.p, c->n_lib,
-             c->has_sr.p, c->split.p, n_split};
-    const unsigned grid = blocks_for(n, 256);
-    // losing pairs: at most one per two records.  Slot 1: keys (u64) x 2 and values (u32) x 2 of the list and its sort buffers
-    const size_t lcap = n / 2 + 8;
-    uint32_t *gs;
-    ELP_TRY(scratch(c, 1, 6 * lcap + 16, &gs));
-    uint64_t *pk = reinterpret_cast<uint64_t *>(gs);
-    uint32_t *pv = gs + 4 * lcap;
-    uint32_t *mailbox = c->err_flag.p + 3;  // the scan-total word: length of the list, then members of large sets, then their candidates
-    ELP_HIP(c, hipMemsetAsync(mailbox, 0, 4, st));
-    const unsigned cgrid = (unsigned)std::min<uint64_t>(2048, (n + DC_STEP - 1) / DC_STEP);
-    const uint64_t chunk = (((n + cgrid - 1) / cgrid) + DC_STEP - 1) / DC_STEP * DC_STEP;
-    ELP_LAUNCH(c, "mx_counters", k_dup_counters, dim3(cgrid), dim3(256), ((size_t)ncell + npr) * sizeof(unsigned int), m, ctr, pair_reads, chunk, pk, pv,
-               mailbox);
-    uint32_t L = 0;
-    ELP_HIP(c, hipMemcpyAsync(&L, mailbox, 4, hipMemcpyDeviceToHost, st));
-    ELP_HIP(c, elp::stream_wait(st));
-    ELP_HIP(c, hipMemsetAsync(mailbox, 0, 4, st));
-    if ((size_t)L > lcap) return set_error(c, ELP_ERR_HIP, "elp_dup_metrics: more losing pairs than pairs");
-    uint32_t total = 0, G = 0;
-    uint64_t *ks = pk;
-    uint32_t *vs = pv, *head = nullptr, *gidx = nullptr, *gstart = nullptr;
-    if (L) {
-      int ndig = 1;
-      while (ndig < 4 && (n >> (8 * ndig)) != 0) ndig++;  // pair groups are record indices < n < 2^32
-      {
-        ProfScope ps(c, "mx_");
-        ELP_TRY(radix_sort_pairs_low(c, pk, pv, pk + lcap, pv + lcap, L, ndig, &ks, &vs));
-      }
-      // the halves the sort left free hold the head flags, the group numbers and the group starts
-      head = reinterpret_cast<uint32_t *>(ks == pk ? pk + lcap : pk);
-      gidx = head + lcap;
-      gstart = vs == pv ? pv + lcap : pv;
-      ELP_LAUNCH(c, "mx_opt_heads", k_opt_heads, dim3(blocks_for(L, 256)), dim3(256), 0, L, (const uint64_t *)ks, head);
-      {
-        ProfScope ps(c, "mx_");
-        ELP_TRY(exclusive_scan_u32(c, head, gidx, L, &G));
-      }
-      ELP_LAUNCH(c, "mx_opt_starts", k_opt_starts, dim3(blocks_for(L, 256)), dim3(256), 0, L, (const uint32_t *)head, (const uint32_t *)gidx, gstart, G);
-      total = L + G;
-    }
-    if (total) {
-      Member *members;
-      uint32_t *wk, *mread;
-      uint2 *ginfo;
-      const size_t tp = ((size_t)total + 7) & ~(size_t)7;
-      ELP_TRY(scratch(c, 2, (size_t)total + 4, &members));
-      ELP_TRY(scratch(c, 3, 12 * tp + 16, &wk));  // parent | mset | linfo | lcount | setcnt (u64) | vals x 2 | keys (u64) x 2
-      ELP_TRY(scratch(c, 4, (size_t)total + 4, &mread));
-      ELP_TRY(scratch(c, 5, (size_t)total + 4, &ginfo));
-      uint32_t *parent = wk, *mset = wk + tp, *linfo = wk + 2 * tp, *lcount = wk + 3 * tp, *lvals = wk + 6 * tp;
-      unsigned long long *setcnt = reinterpret_cast<unsigned long long *>(wk + 4 * tp);
-      uint64_t *lkeys = reinterpret_cast<uint64_t *>(wk + 8 * tp);
-      ELP_HIP(c, hipMemsetAsync(ginfo, 0, (size_t)total * sizeof(uint2), st));
-      ELP_HIP(c, hipMemsetAsync(linfo, 0, 4 * tp * sizeof(uint32_t), st));  // linfo, lcount, setcnt
-      ELP_LAUNCH(c, "mx_opt_slots", k_opt_slots, dim3(blocks_for(L, 256)), dim3(256), 0, m, L, (const uint64_t *)ks, (const uint32_t *)vs,
-                 (const uint32_t *)head, (const uint32_t *)gidx, (const uint32_t *)gstart, mread, ginfo, mset);
-      ELP_LAUNCH(c, "mx_opt_fill", k_opt_fill, dim3(blocks_for(total, 256)), dim3(256), 0, m, total, (const uint32_t *)mread, members);
-      ELP_LAUNCH(c, "mx_opt_eval", k_opt_eval, dim3(std::min(blocks_for(total, 128), 2048u)), dim3(128),
-                 (size_t)(c->n_lib + 1) * (1 + (hist ? 3 * (size_t)lds_bins : 0)) * sizeof(unsigned int), m, total, (const uint2 *)ginfo,
-                 (const Member *)members, parent, (long long)dist, ctr, c->err_flag.p, hist, hist_len, lds_bins, linfo, lcount, mailbox);
-      uint32_t n_large = 0;
-      ELP_HIP(c, hipMemcpyAsync(&n_large, mailbox, 4, hipMemcpyDeviceToHost, st));
-      ELP_HIP(c, elp::stream_wait(st));
-      ELP_HIP(c, hipMemsetAsync(mailbox, 0, 4, st));
-      if (n_large) {
-        ELP_LAUNCH(c, "mx_large_list", k_large_list, dim3(blocks_for(total, 256)), dim3(256), 0, total, (const uint32_t *)mset, (const uint32_t *)linfo,
-                   (const Member *)members, lkeys, lvals, mailbox);
-        uint32_t cl = 0;
-        ELP_HIP(c, hipMemcpyAsync(&cl, mailbox, 4, hipMemcpyDeviceToHost, st));
-        ELP_HIP(c, elp::stream_wait(st));
-        ELP_HIP(c, hipMemsetAsync(mailbox, 0, 4, st));
-        if (cl) {
-          uint64_t *ks;
-          uint32_t *vs;
-          ProfScope ps(c, "mx_large_");
-          ELP_TRY(radix_sort_pairs(c, lkeys, lvals, lkeys + tp, lvals + tp, cl, &ks, &vs));
-          ELP_LAUNCH(c, "mx_large_iota", k_iota32, dim3(blocks_for(cl, 256)), dim3(256), 0, parent, cl);
-          ELP_LAUNCH(c, "mx_large_union", k_large_union, dim3(blocks_for(cl, 256)), dim3(256), 0, cl, (const uint64_t *)ks, (const uint32_t *)vs,
-                     (const uint32_t *)mset, (const Member *)members, (long long)dist, parent);
-          ELP_LAUNCH(c, "mx_large_roots", k_large_roots, dim3(blocks_for(cl, 256)), dim3(256), 0, cl, (const uint32_t *)vs, (const uint32_t *)mset,
-                     (const uint32_t *)parent, setcnt);
-        }
-        ELP_LAUNCH(c, "mx_large_final", k_large_final, dim3(blocks_for(total, 256)), dim3(256), 0, m, total, (const uint2 *)ginfo, (const uint32_t *)linfo,
-                   (const uint32_t *)lcount, (const unsigned long long *)setcnt, ctr, hist, hist_len);
-      }
-    }
-    if (hist)
-      ELP_LAUNCH(c, "mx_origin_count", k_origin_count, dim3(std::min(grid, 2048u)), dim3(256), (c->n_lib + 1) * sizeof(unsigned int), m, origins);
+// ---- host side: a call is a sequence of phases over one work struct.  Sizes, offsets, grids and LDS bytes come from metrics_plan.hpp.
+struct MxWork {
+  MxSizes S;
+  MxCols m;
+  long long dist;
+  hipStream_t st;
+  unsigned long long *ctr = nullptr, *origins = nullptr, *hist = nullptr, *pair_reads = nullptr;  // the counter block (hist: null if not asked for)
+  // one word of the error block, zero between its uses: the length of the loser list, then the members of large sets, then their candidates
+  uint32_t *mailbox;
+  uint32_t *list = nullptr;  // slot 1
+  uint64_t *ks = nullptr;    // the loser list, sorted by pair group from mx_groups on
+  uint32_t *vs = nullptr, *head = nullptr, *gidx = nullptr, *gstart = nullptr;
+  uint32_t L = 0, G = 0, total = 0, n_large = 0;  // read back: losers, pair groups, member slots (L + G), members of large sets
+  Member *members = nullptr;  // slots 2 .. 5
+  uint32_t *sets = nullptr, *mread = nullptr;
+  uint2 *ginfo = nullptr;
+  MxWork(elp_ctx *c, int d, int hist_len)
+      : S(c->n, c->n_lib, (int)c->max_split + 1, hist_len),
+        m{c->n, c->refid.p, c->flag.p, c->rgid.p, c->rg_lib.p, c->upos.p, c->qname_off.p, c->qname.p, c->mate.p, c->pair_win.p, c->n_lib,
+          c->has_sr.p, c->split.p, (int)c->max_split + 1},
+        dist(d), st(c->stream), mailbox(c->err_flag.p + MX_MAILBOX_WORD) {}
+  uint64_t *keys_at(size_t word) const { return reinterpret_cast<uint64_t *>(list + word); }  // 64-bit keys at a word offset of slot 1
+};
+
+// a count a kernel left in the mailbox word comes to the host, and the word is zero again for its next use
+static int mx_take(elp_ctx *c, MxWork &w, uint32_t *count) {
+  ELP_HIP(c, hipMemcpyAsync(count, w.mailbox, sizeof(uint32_t), hipMemcpyDeviceToHost, w.st));
+  ELP_HIP(c, elp::stream_wait(w.st));
+  ELP_HIP(c, hipMemsetAsync(w.mailbox, 0, sizeof(uint32_t), w.st));
+  return 0;
+}
+
+// the counter block, zeroed (also for a call without records)
+static int mx_block(elp_ctx *c, MxWork &w) {
+  ELP_TRY(scratch(c, 0, w.S.block, &w.ctr));
+  w.origins = w.ctr + w.S.origins;
+  w.hist = w.S.hist_len ? w.ctr + w.S.hist : nullptr;
+  w.pair_reads = w.ctr + w.S.pair_reads;
+  ELP_HIP(c, hipMemsetAsync(w.ctr, 0, w.S.cells * sizeof(unsigned long long), w.st));
+  return 0;
+}
+
+// phase 1: the counters, and the list of the losing pairs -> L
+static int mx_counters(elp_ctx *c, MxWork &w) {
+  const MxListScratch ls(w.S.lcap);
+  ELP_TRY(scratch(c, 1, ls.words, &w.list));
+  w.ks = w.keys_at(ls.pk);
+  w.vs = w.list + ls.pv;
+  ELP_HIP(c, hipMemsetAsync(w.mailbox, 0, sizeof(uint32_t), w.st));
+  ELP_LAUNCH(c, "mx_counters", k_dup_counters, dim3(w.S.counters_grid), dim3(256), w.S.counters_lds, w.m, w.ctr, w.pair_reads, w.S.chunk, w.ks, w.vs,
+             w.mailbox);
+  ELP_TRY(mx_take(c, w, &w.L));
+  if ((size_t)w.L > w.S.lcap) return set_error(c, ELP_ERR_HIP, "elp_dup_metrics: more losing pairs than pairs");
+  return 0;
+}
+
+// phase 2: the list sorted by pair group; a group's losers are a run: head flags, group numbers, group starts -> G, total
+static int mx_groups(elp_ctx *c, MxWork &w) {
+  const MxListScratch ls(w.S.lcap);
+  uint64_t *const pk = w.ks;
+  uint32_t *const pv = w.vs;
+  {
+    ProfScope ps(c, "mx_");
+    ELP_TRY(radix_sort_pairs_low(c, pk, pv, w.keys_at(ls.keys_half(false)), w.list + ls.vals_half(false), w.L, w.S.ndig, &w.ks, &w.vs));
   }
-  std::vector<unsigned long long> h((size_t)ncell + norg + nhist + npr);
-  ELP_HIP(c, hipMemcpyAsync(h.data(), ctr, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  const MxListScratch::Groups g = ls.groups(w.ks == pk, w.vs == pv);
+  w.head = w.list + g.head;
+  w.gidx = w.list + g.gidx;
+  w.gstart = w.list + g.gstart;
+  const unsigned grid = ls.grid(w.L);
+  ELP_LAUNCH(c, "mx_opt_heads", k_opt_heads, dim3(grid), dim3(256), 0, w.L, (const uint64_t *)w.ks, w.head);
+  {
+    ProfScope ps(c, "mx_");
+    ELP_TRY(exclusive_scan_u32(c, w.head, w.gidx, w.L, &w.G));
+  }
+  ELP_LAUNCH(c, "mx_opt_starts", k_opt_starts, dim3(grid), dim3(256), 0, w.L, (const uint32_t *)w.head, (const uint32_t *)w.gidx, w.gstart, w.G);
+  w.total = w.L + w.G;
+  return 0;
+}
+
+// phase 3: a slot per member (every group's origin, then its losers), the members' tiles, the sets of up to OPT_SMALL members -> n_large
+static int mx_small_sets(elp_ctx *c, MxWork &w) {
+  const MxSetScratch ss(w.total);
+  ELP_TRY(scratch(c, 2, ss.members, &w.members));
+  ELP_TRY(scratch(c, 3, ss.words3, &w.sets));
+  ELP_TRY(scratch(c, 4, ss.mread, &w.mread));
+  ELP_TRY(scratch(c, 5, ss.ginfo, &w.ginfo));
+  ELP_HIP(c, hipMemsetAsync(w.ginfo, 0, ss.total * sizeof(uint2), w.st));
+  ELP_HIP(c, hipMemsetAsync(w.sets + ss.zero, 0, ss.zero_words * sizeof(uint32_t), w.st));  // linfo, lcount, setcnt
+  ELP_LAUNCH(c, "mx_opt_slots", k_opt_slots, dim3(MxListScratch::grid(w.L)), dim3(256), 0, w.m, w.L, (const uint64_t *)w.ks, (const uint32_t *)w.vs,
+             (const uint32_t *)w.head, (const uint32_t *)w.gidx, (const uint32_t *)w.gstart, w.mread, w.ginfo, w.sets + ss.mset);
+  ELP_LAUNCH(c, "mx_opt_fill", k_opt_fill, dim3(ss.member_grid), dim3(256), 0, w.m, w.total, (const uint32_t *)w.mread, w.members);
+  ELP_LAUNCH(c, "mx_opt_eval", k_opt_eval, dim3(ss.eval_grid), dim3(MX_EVAL_THREADS), w.S.eval_lds, w.m, w.total, (const uint2 *)w.ginfo,
+             (const Member *)w.members, w.sets + ss.parent, w.dist, w.ctr, c->err_flag.p, w.hist, w.S.hist_len, w.S.lds_bins, w.sets + ss.linfo,
+             w.sets + ss.lcount, w.mailbox);
+  return mx_take(c, w, &w.n_large);
+}
+
+// phase 4: the sets of more than OPT_SMALL members: their members that can have an optical partner at all (cl of them) sorted by bucket
+// hash, joined in a union-find, the roots counted per set; then every large set accounts for itself
+static int mx_large_sets(elp_ctx *c, MxWork &w) {
+  const MxSetScratch ss(w.total);
+  uint32_t *parent = w.sets + ss.parent, *mset = w.sets + ss.mset, *linfo = w.sets + ss.linfo, *lcount = w.sets + ss.lcount, *lvals = w.sets + ss.lvals;
+  unsigned long long *setcnt = reinterpret_cast<unsigned long long *>(w.sets + ss.setcnt);
+  uint64_t *lkeys = reinterpret_cast<uint64_t *>(w.sets + ss.lkeys);
+  ELP_LAUNCH(c, "mx_large_list", k_large_list, dim3(ss.member_grid), dim3(256), 0, w.total, (const uint32_t *)mset, (const uint32_t *)linfo,
+             (const Member *)w.members, lkeys, lvals, w.mailbox);
+  uint32_t cl = 0;
+  ELP_TRY(mx_take(c, w, &cl));
+  if (cl) {
+    uint64_t *ks;
+    uint32_t *vs;
+    const unsigned grid = ss.cand_grid(cl);
+    ProfScope ps(c, "mx_large_");
+    ELP_TRY(radix_sort_pairs(c, lkeys, lvals, reinterpret_cast<uint64_t *>(w.sets + ss.lkeys_tmp), w.sets + ss.lvals_tmp, cl, &ks, &vs));
+    ELP_LAUNCH(c, "mx_large_iota", k_iota32, dim3(grid), dim3(256), 0, parent, cl);
+    ELP_LAUNCH(c, "mx_large_union", k_large_union, dim3(grid), dim3(256), 0, cl, (const uint64_t *)ks, (const uint32_t *)vs, (const uint32_t *)mset,
+               (const Member *)w.members, w.dist, parent);
+    ELP_LAUNCH(c, "mx_large_roots", k_large_roots, dim3(grid), dim3(256), 0, cl, (const uint32_t *)vs, (const uint32_t *)mset, (const uint32_t *)parent,
+               setcnt);
+  }
+  ELP_LAUNCH(c, "mx_large_final", k_large_final, dim3(ss.member_grid), dim3(256), 0, w.m, w.total, (const uint2 *)w.ginfo, (const uint32_t *)linfo,
+             (const uint32_t *)lcount, (const unsigned long long *)setcnt, w.ctr, w.hist, w.S.hist_len);
+  return 0;
+}
+
+// phase 5 (histograms only): the pair groups per library; the ones without duplicates are the sets of one read (mx_finish)
+static int mx_origins(elp_ctx *c, MxWork &w) {
+  ELP_LAUNCH(c, "mx_origin_count", k_origin_count, dim3(w.S.origin_grid), dim3(256), w.S.origin_lds, w.m, w.origins);
+  return 0;
+}
+
+// phase 6: the block and the error words come back; a name that the reference would have panicked on fails the call
+static int mx_read_back(elp_ctx *c, MxWork &w, int64_t *counters_host, int64_t *hist_host) {
+  std::vector<unsigned long long> h(w.S.cells);
+  ELP_HIP(c, hipMemcpyAsync(h.data(), w.ctr, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, w.st));
   uint32_t e[4];
   ELP_TRY(fetch_err(c, e));
-  if (e[2]) {
-    ELP_HIP(c, hipMemsetAsync(c->err_flag.p + 2, 0, 4, st));
+  if (e[MX_NAME_ERR_WORD]) {
+    ELP_HIP(c, hipMemsetAsync(c->err_flag.p + MX_NAME_ERR_WORD, 0, sizeof(uint32_t), w.st));
     return set_error(c, ELP_ERR_DATA, "QNAME tile/x/y field is not an integer (reference: internal.ParseInt panics, filters/mark-optical-duplicates.go:55-61)");
   }
-  for (int l = 0; l <= c->n_lib; l++)
-    for (int k = 0; k < ELP_NCTR; k++) counters_host[l * ELP_NCTR + k] = (int64_t)h[l * ELP_NCTR + k];
-  // ReadPairsExamined counts reads, then halves (:504-506) - per filter run, i.e. per split file
-  for (int l = 0; l <= c->n_lib; l++) {
-    int64_t pairs = 0;
-    for (int sp = 0; sp < n_split; sp++) pairs += (int64_t)(h[(size_t)ncell + norg + nhist + (size_t)sp * (c->n_lib + 1) + l] / 2);
-    counters_host[l * ELP_NCTR + 1] = pairs;
-  }
-  if (hist_host) {
-    // the device counted the sets that have duplicates; an origin without duplicates is a set of one read, none of them optical
-    const unsigned long long *ho = h.data() + ncell, *hh = ho + norg;
-    for (int l = 0; l <= c->n_lib; l++) {
-      int64_t *out = hist_host + (size_t)l * 3 * hist_len;
-      unsigned long long with_dups = 0;
-      for (size_t k = 0; k < (size_t)3 * hist_len; k++) out[k] = (int64_t)hh[(size_t)l * 3 * hist_len + k];
-      for (int b = 0; b < hist_len; b++) with_dups += hh[(size_t)l * 3 * hist_len + b];
-      const int64_t alone = (int64_t)(ho[l] - with_dups);
-      const int one = 1 < hist_len ? 1 : hist_len - 1;
-      out[one] += alone;             // duplicatesCountHistogram[1]
-      out[hist_len + one] += alone;  // nonOpticalDuplicatesCountHistogram[1]
-    }
-  }
+  mx_finish(w.S, h.data(), counters_host, hist_host);
   return 0;
+}
+
+static int metrics_impl(elp_ctx *c, int dist, int64_t *counters_host, int64_t *hist_host, int hist_len) {
+  MxWork w(c, dist, hist_host ? hist_len : 0);
+  if (w.S.lds_refused)
+    return set_error(c, ELP_ERR_UNSUPPORTED, "elp_dup_metrics: %d split ids x %d libraries in one context", w.S.n_split, c->n_lib + 1);
+  ELP_TRY(mx_block(c, w));
+  if (w.S.n) {
+    ELP_TRY(mx_counters(c, w));
+    if (w.L) ELP_TRY(mx_groups(c, w));
+    if (w.total) {
+      ELP_TRY(mx_small_sets(c, w));
+      if (w.n_large) ELP_TRY(mx_large_sets(c, w));
+    }
+    if (w.hist) ELP_TRY(mx_origins(c, w));
+  }
+  return mx_read_back(c, w, counters_host, hist_host);
 }
 
 }  // namespace elp
@@ -658,11 +630,12 @@ static int metrics_on_side(elp_ctx *c, int dist, int64_t *counters_host, int64_t
   ELP_TRY(side_lane(c, 0, &s));
   s->n = c->n; s->n_lib = c->n_lib; s->n_rg = c->n_rg; s->n_ref = c->n_ref; s->max_split = c->max_split; s->derived.marked = c->derived.marked;
   s->n_sr = c->n_sr; s->n_filtered = c->n_filtered;
-  s->flag.p = c->flag.p; s->rgid.p = c->rgid.p; s->rg_lib.p = c->rg_lib.p; s->refid.p = c->refid.p; s->qname_off.p = c->qname_off.p; s->qname.p = c->qname.p;
-  s->pair_win.p = c->pair_win.p; s->mate.p = c->mate.p; s->has_sr.p = c->has_sr.p; s->upos.p = c->upos.p; s->split.p = c->split.p;
-  const int rc = metrics_impl(s, dist, counters_host, hist_host, hist_len);
-  s->flag.p = nullptr; s->rgid.p = nullptr; s->rg_lib.p = nullptr; s->refid.p = nullptr; s->qname_off.p = nullptr; s->qname.p = nullptr;
-  s->pair_win.p = nullptr; s->mate.p = nullptr; s->has_sr.p = nullptr; s->upos.p = nullptr; s->split.p = nullptr;
+  int rc;
+  {
+    LaneViews views(s, c, &elp_ctx::flag, &elp_ctx::rgid, &elp_ctx::rg_lib, &elp_ctx::refid, &elp_ctx::qname_off, &elp_ctx::qname,
+                    &elp_ctx::pair_win, &elp_ctx::mate, &elp_ctx::has_sr, &elp_ctx::upos, &elp_ctx::split);
+    rc = metrics_impl(s, dist, counters_host, hist_host, hist_len);
+  }
   if (rc != 0) {
     (void)elp::stream_wait(s->stream);
     c->err = s->err;

@@ -233,11 +233,12 @@ static int sort_queryname(elp_ctx *c) {
   elp_ctx *s = nullptr;
   ELP_TRY(side_lane(c, 1, &s));
   s->n = c->n; s->n_sr = c->n_sr; s->max_qname_len = c->max_qname_len;
-  s->qname_off.p = c->qname_off.p; s->qname.p = c->qname.p; s->has_sr.p = c->has_sr.p;
-  s->perm.p = c->perm.p; s->perm.cap = c->perm.cap;
-  int rc = qname_sort_impl(s);
-  s->qname_off.p = nullptr; s->qname.p = nullptr; s->has_sr.p = nullptr;
-  s->perm.p = nullptr; s->perm.cap = 0;
+  int rc;
+  {
+    LaneViews views(s, c, &elp_ctx::qname_off, &elp_ctx::qname, &elp_ctx::has_sr);
+    views.view(s->perm, c->perm, true);
+    rc = qname_sort_impl(s);
+  }
   if (rc == 0) rc = radix_check(s);  // (the lane's own error words: a look-back timeout of its passes is read here)
   if (rc != 0) {
     (void)elp::stream_wait(s->stream);

@@ -652,17 +652,17 @@ static int sort_on_side(elp_ctx *c) {
   s->n_ref = c->n_ref;
   s->derived = elp::Derived{};
   s->derived.keys = true;  // (of what the context has derived the shadow sees the key column, nothing else)
-  s->key.p = c->key.p; s->flag.p = c->flag.p; s->mapq.p = c->mapq.p; s->next_refid.p = c->next_refid.p; s->pnext.p = c->pnext.p; s->tlen.p = c->tlen.p;
-  s->qname_off.p = c->qname_off.p; s->qname.p = c->qname.p; s->has_sr.p = c->has_sr.p;
-  s->perm.p = c->perm.p; s->perm.cap = c->perm.cap;
   // the key passes may have been queued ahead (elp_sort_ahead, from inside elp_mark_duplicates): same keys, same length, same lane
   const bool pre_ok = c->presort_ks && c->derived.presorted && c->presort_n == c->n && c->presort_idx_bits == index_bits(c->n) && c->tune.sort_pairs != 1;
   uint64_t *pre = pre_ok ? c->presort_ks : nullptr;
   c->derived.drop_presort();  // (used once: the tie-break leaves its marks in the buffer's other half)
-  int rc = sort_impl(s, pre);
-  s->key.p = nullptr; s->flag.p = nullptr; s->mapq.p = nullptr; s->next_refid.p = nullptr; s->pnext.p = nullptr; s->tlen.p = nullptr;
-  s->qname_off.p = nullptr; s->qname.p = nullptr; s->has_sr.p = nullptr;
-  s->perm.p = nullptr; s->perm.cap = 0;
+  int rc;
+  {
+    LaneViews views(s, c, &elp_ctx::key, &elp_ctx::flag, &elp_ctx::mapq, &elp_ctx::next_refid, &elp_ctx::pnext, &elp_ctx::tlen, &elp_ctx::qname_off,
+                    &elp_ctx::qname, &elp_ctx::has_sr);
+    views.view(s->perm, c->perm, true);
+    rc = sort_impl(s, pre);
+  }
   if (rc == 0) rc = radix_check(s);  // (the lane's own error words: nothing of the sort stays unread)
   if (rc != 0) {
     (void)elp::stream_wait(s->stream);

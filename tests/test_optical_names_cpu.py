@@ -65,11 +65,10 @@ def test_column_counts(ncol):
     assert _checked(nm) == on.go_tile_info(nm)
 
 
-def test_random_names_sweep():
-    """120 000 names over the alphabets of the hand table (digits, signs, zero padding, spaces, '_', 'x', a non-ASCII digit, empty
-    fields) with 0..9 colons, against the restatement.  Every class is reached: valid, syntax error, range error, 5 columns, 7
-    columns, other counts.  Fails on the parent commit's oracle (range errors, panic flag)."""
-    rng = np.random.default_rng(2026)
+def sweep_names(count, seed=2026):
+    """(columns, name) of `count` random names over the alphabets of the hand table (digits, signs, zero padding, spaces, '_', 'x', a
+    non-ASCII digit, empty fields) with 0..9 colons"""
+    rng = np.random.default_rng(seed)
     junk = [b" ", b"_", b"x", b"+", b"-", "٣".encode(), b"."]
     big = [str(v).encode() for v in on.EDGE_VALUES] + [b"9223372036854775808", b"18446744073709551616", b"-9223372036854775809"]
 
@@ -92,10 +91,17 @@ def test_random_names_sweep():
             s = s[:k] + junk[int(rng.integers(0, len(junk)))] + s[k:]
         return s
 
-    seen = {"valid": 0, "syntax": 0, "range": 0, "5": 0, "7": 0, "other": 0}
-    for _ in range(120_000):
+    for _ in range(count):
         ncol = int(rng.choice([5, 7, 5, 7, 1, 2, 3, 4, 6, 8, 9, 10]))
-        nm = b":".join(field() for _ in range(ncol))
+        yield ncol, b":".join(field() for _ in range(ncol))
+
+
+def test_random_names_sweep():
+    """120 000 names over the alphabets of the hand table (digits, signs, zero padding, spaces, '_', 'x', a non-ASCII digit, empty
+    fields) with 0..9 colons, against the restatement.  Every class is reached: valid, syntax error, range error, 5 columns, 7
+    columns, other counts.  Fails on the parent commit's oracle (range errors, panic flag)."""
+    seen = {"valid": 0, "syntax": 0, "range": 0, "5": 0, "7": 0, "other": 0}
+    for ncol, nm in sweep_names(120_000):
         want = on.go_tile_info(nm)
         assert _checked(nm) == want, nm
         seen[str(ncol) if ncol in (5, 7) else "other"] += 1
