@@ -80,7 +80,7 @@ struct elp_ctx {
   std::vector<uint16_t> h_rg_lib, h_rg_cov;
   elp::DVec<int32_t> ref_len;
   elp::DVec<uint16_t> rg_lib, rg_cov;
-  // elp_replace_reference_dictionary (filter.hip): n_ref / h_ref_len / ref_len above hold the NEW dictionary while dict_replaced; the one
+  // elp_replace_reference_dictionary (dictionary.hip): n_ref / h_ref_len / ref_len above hold the NEW dictionary while dict_replaced; the one
   // elp_set_header gave is kept here, elp_reset returns to it (the staged bytes of the next file carry the header's refids again)
   bool dict_replaced = false;
   int32_t n_ref0 = 0;
@@ -505,14 +505,12 @@ __host__ __device__ inline uint16_t mod_flag(uint16_t flag) {
   return flag;
 }
 
-// SplitFilePerChromosome's routing rule (sam/split-merge.go:280-293) for a record with these refids: *g = its split file - 0 for RNAME "*"
-// (contigToGroup["*"] = "unmapped", :254), else group_of_ref[refid] -; returns whether it also goes to the spread file (:286: RNEXT != "=",
-// which in BAM is next_refid != refid (sam/bam-files.go:344-346), RNAME != "*", and the mate's group differs - so a mapped record with RNEXT
-// "*" is spread).  elp_split_classify (filter.hip) and the split emitters' list (split.hip) route by it.
-__device__ __forceinline__ bool split_route(int32_t r, int32_t nr, const int32_t *__restrict__ group_of_ref, int32_t n_ref, int32_t *g) {
-  *g = (r >= 0 && r < n_ref) ? group_of_ref[r] : 0;
-  const int32_t gn = (nr >= 0 && nr < n_ref) ? group_of_ref[nr] : 0;
-  return nr != r && r >= 0 && gn != *g;
+// What a filter that rejected records leaves in the context's counts (filter.hip, dictionary.hip): `dropped` live records leave the
+// output like the tagged copies do; they and the `tagged` rejected sr-tagged copies are state-2 records, none of them a
+// duplicate-marking candidate.  The caller invalidates what it made stale (c->derived).
+inline void commit_rejects(elp_ctx *c, unsigned long long dropped, unsigned long long tagged) {
+  c->n_sr += dropped;
+  c->n_filtered += dropped + tagged;
 }
 
 // ---- cross-TU entry points ----
@@ -560,8 +558,8 @@ int stage_reserve(elp_ctx *c, uint64_t n, uint64_t qb, uint64_t co, uint64_t sb,
 // context's output, or MERGE_SECOND | its rank in the second's
 constexpr uint32_t MERGE_SECOND = 0x80000000u;
 int keep_concat_src(elp_ctx *groups, uint64_t ng, uint64_t ns, uint32_t *g0_dev, uint32_t *src);  // keep.hip: the unsorted merge's stream as such an array
-int merge_refuses_queryname(elp_ctx *groups, const char *who);  // filter.hip: ELP_ERR_UNSUPPORTED (cmd/merge.go:175-176)
-int merge_spread_slots(elp_ctx *groups, elp_ctx *spread, uint64_t **slots_out);  // filter.hip: the merge order as ranks, on the device  // grows the staged columns (ctx.hip)
+int merge_refuses_queryname(elp_ctx *groups, const char *who);  // split_merge.hip: ELP_ERR_UNSUPPORTED (cmd/merge.go:175-176)
+int merge_spread_slots(elp_ctx *groups, elp_ctx *spread, uint64_t **slots_out);  // split_merge.hip: the merge order as ranks, on the device  // grows the staged columns (ctx.hip)
 int stage_recode_seq(elp_ctx *c, uint64_t from, uint64_t bytes);
 inline void clear_run_settings(elp_ctx *c) { c->tag_filter = false; c->replace_rg = false; c->replace_rg_id.clear(); }  // elp_reset, elp_set_header
 inline bool same_replace_rg(const elp_ctx *a, const elp_ctx *b) { return a->replace_rg == b->replace_rg && a->replace_rg_id == b->replace_rg_id; }

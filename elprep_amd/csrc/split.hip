@@ -1,5 +1,5 @@
 // split.hip — the files of `elprep split`, written on the device: SplitFilePerChromosome (sam/split-merge.go:225-311) and
-// SplitSingleEndFilePerChromosome (:664-724) with payloads.  elp_split_classify (filter.hip) is the routing rule as three small arrays and
+// SplitSingleEndFilePerChromosome (:664-724) with payloads.  elp_split_classify (split_merge.hip) is the routing rule as three small arrays and
 // elp_copy_records / elp_exchange_records (exchange.hip) deliver records to other contexts; here the records of ONE reader context leave as
 // the bytes of the split files themselves - BAM records, BGZF members or SAM lines - so that a host writes `elprep split`'s output without
 // re-encoding a payload.
@@ -24,6 +24,7 @@
 
 #include "common.hpp"
 #include "bamout.hpp"
+#include "filter_rules.hpp"  // split_route
 
 namespace elp {
 

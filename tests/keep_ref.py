@@ -10,7 +10,7 @@ import numpy as np
 # sizes the GPU tests place their seams at (tests/test_keep_order_cpu.py checks them against the sources that state them)
 KEEP_W = 512          # records per workgroup of the two partition kernels, csrc/keep.hip
 SCAN_TILE = 2048      # counts per workgroup of exclusive_scan_u32, csrc/radix.hip (256 threads * SCAN_ITEMS)
-MERGE_CHECK_W = 256   # entries per workgroup of the merge's order check, csrc/filter.hip
+MERGE_CHECK_W = 256   # entries per workgroup of the merge's order check, csrc/split_merge.hip
 
 
 def keep_order(state, split=None, by_split=False):

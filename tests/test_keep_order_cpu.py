@@ -46,7 +46,7 @@ def test_the_seam_sizes_of_the_gpu_tests_are_the_sources():
     import re
     src = lambda f: open(os.path.join(ROOT, "elprep_amd", "csrc", f)).read()
     assert int(re.search(r"constexpr uint32_t KEEP_W = (\d+);", src("keep.hip")).group(1)) == keep_ref.KEEP_W
-    assert int(re.search(r"constexpr uint32_t MERGE_CHECK_W = (\d+);", src("filter.hip")).group(1)) == keep_ref.MERGE_CHECK_W
+    assert int(re.search(r"constexpr uint32_t MERGE_CHECK_W = (\d+);", src("split_merge.hip")).group(1)) == keep_ref.MERGE_CHECK_W
     radix = src("radix.hip")
     assert "constexpr int SCAN_TILE = 256 * SCAN_ITEMS;" in radix
     assert 256 * int(re.search(r"constexpr int SCAN_ITEMS = (\d+);", radix).group(1)) == keep_ref.SCAN_TILE
