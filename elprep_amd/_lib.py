@@ -32,6 +32,7 @@ HIP_SYMBOLS = [
     "elp_order_keep", "elp_emit_merged_bgzf", "elp_emit_concat_bam", "elp_emit_concat_bgzf",
     "elp_set_reference_names_flat", "elp_emit_sorted_sam", "elp_emit_merged_sam", "elp_emit_concat_sam", "elp_stage_sam",
     "elp_emit_split_bam", "elp_emit_split_bgzf", "elp_emit_split_sam",
+    "elp_index_sorted_bgzf", "elp_index_merged_bgzf",
     "elp_snapshot", "elp_rollback", "elp_set_tuning", "elp_profile_enable", "elp_profile_reset", "elp_profile_count", "elp_profile_get", "elp_debug_check_guards",
 ]
 HOST_SYMBOLS = [
@@ -149,7 +150,13 @@ def hip() -> C.CDLL:
             if ELP_AB_BUILD and not hasattr(L, name):
                 continue
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
-        L.elp_copy_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int]
+        # (an older build named by ELP_HIP_SO for A/B timing lacks the index calls; calling one of them there fails with AttributeError)
+        for name, args in (("elp_index_sorted_bgzf", [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+                           ("elp_index_merged_bgzf", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)])):
+            if ELP_AB_BUILD and not hasattr(L, name):
+                continue
+            getattr(L, name).argtypes = args
+        L.elp_copy_records.argtypes =[C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int]
         L.elp_group_init_transport.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.elp_group_set_p2p.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.elp_exchange_records.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int]

@@ -97,5 +97,9 @@ int emit_stream(elp_ctx *c, const BamOut &m, const BamOut &m2, const uint32_t *s
 BamOut bam_out_of(const elp_ctx *c);
 SamNames sam_names_of(const elp_ctx *c);
 int sam_names_checks(elp_ctx *c, elp_ctx *other, const char *who);
+// emit.hip, for the index of a stream (bai.hip): what a replacing read group may add to a staged record, and the merged stream as
+// elp_emit_merged_* walks it - its checks, both contexts' columns and the list `src` (scratch slot 6 of `groups`; nullptr for n_out = 0)
+uint64_t emit_out_growth(const elp_ctx *c);
+int emit_merged_list(elp_ctx *groups, elp_ctx *spread, const char *who, BamOut *mg, BamOut *ms, const uint32_t **src, uint64_t *n_out);
 
 }  // namespace elp

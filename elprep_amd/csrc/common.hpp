@@ -560,6 +560,8 @@ constexpr uint32_t MERGE_SECOND = 0x80000000u;
 int keep_concat_src(elp_ctx *groups, uint64_t ng, uint64_t ns, uint32_t *g0_dev, uint32_t *src);  // keep.hip: the unsorted merge's stream as such an array
 int merge_refuses_queryname(elp_ctx *groups, const char *who);  // split_merge.hip: ELP_ERR_UNSUPPORTED (cmd/merge.go:175-176)
 int merge_spread_slots(elp_ctx *groups, elp_ctx *spread, uint64_t **slots_out);  // split_merge.hip: the merge order as ranks, on the device  // grows the staged columns (ctx.hip)
+// split_merge.hip: the order check merge_spread_slots makes on a keep-ordered side, for one context (keys: n_out words, bad_dev: one, of the caller's scratch)
+int keep_coordinate_order(elp_ctx *c, uint64_t n_out, uint64_t *keys, uint32_t *bad_dev, bool *in_order);
 int stage_recode_seq(elp_ctx *c, uint64_t from, uint64_t bytes);
 inline void clear_run_settings(elp_ctx *c) { c->tag_filter = false; c->replace_rg = false; c->replace_rg_id.clear(); }  // elp_reset, elp_set_header
 inline bool same_replace_rg(const elp_ctx *a, const elp_ctx *b) { return a->replace_rg == b->replace_rg && a->replace_rg_id == b->replace_rg_id; }

@@ -133,17 +133,23 @@ static int two_context_checks(elp_ctx *groups, elp_ctx *spread, const char *who)
     return set_error(groups, ELP_ERR_ARG, "%s: one context has replaced its reference dictionary, the other has not (elp_replace_reference_dictionary)", who);
   return 0;
 }
+// the columns of both contexts as the kernels of a stream of two take them
+static void two_columns(elp_ctx *groups, elp_ctx *spread, BamOut *mg, BamOut *ms) {
+  *mg = bam_out_of(groups);
+  *ms = bam_out_of(spread);
+  ms->drop = mg->drop; ms->rg_new = mg->rg_new;  // (equal contents, checked by two_context_checks; both on this device)
+}
 static int emit_two(elp_ctx *groups, elp_ctx *spread, const uint32_t *src, uint64_t n_out, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out, OutFormat fmt,
                     const char *who) {
-  const BamOut mg = bam_out_of(groups);
-  BamOut ms = bam_out_of(spread);
-  ms.drop = mg.drop; ms.rg_new = mg.rg_new;  // (equal contents, checked by two_context_checks; both on this device)
+  BamOut mg, ms;
+  two_columns(groups, spread, &mg, &ms);
   const SamNames nm = fmt == OutFormat::SAM ? sam_names_of(groups) : SamNames{};  // (equal in both contexts: sam_names_checks)
   return emit_stream(groups, mg, ms, src, n_out, std::max(groups->max_raw_rec, spread->max_raw_rec) + out_growth(groups), out, cap, n_bytes_out, fmt, nm, who);
 }
 
-static int emit_merged(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out, OutFormat fmt, const char *who) {
-  if (!groups || !spread || groups == spread || !n_bytes_out) return ELP_ERR_ARG;
+// the merged stream's checks and its list: *src_out (scratch slot 6 of `groups`, n_out entries, queued on its stream) names output record
+// k as out_source reads it; an empty stream has no list.  The emitters below and the index of their stream (bai.hip) walk the same one.
+static int merged_list(elp_ctx *groups, elp_ctx *spread, OutFormat fmt, const char *who, const uint32_t **src_out, uint64_t *n_out_p) {
   if (groups->derived.sorted_qname || spread->derived.sorted_qname) return merge_refuses_queryname(groups, who);
   ELP_TRY(two_context_checks(groups, spread, who));
   if (fmt == OutFormat::SAM) ELP_TRY(sam_names_checks(groups, spread, who));
@@ -151,7 +157,9 @@ static int emit_merged(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t 
   ELP_TRY(merge_spread_slots(groups, spread, &slots));  // checks: both coordinate-sorted or keep-ordered (then: monotonic), one device
   const uint64_t ng = groups->n - groups->n_sr, ns = spread->n - spread->n_sr, n_out = ng + ns;
   if (n_out >= MERGE_SECOND) return set_error(groups, ELP_ERR_UNSUPPORTED, "%s: more than 2^31 output records", who);
-  if (n_out == 0) { *n_bytes_out = 0; return 0; }
+  *n_out_p = n_out;
+  *src_out = nullptr;
+  if (n_out == 0) return 0;
   uint32_t *w;
   ELP_TRY(scratch(groups, 6, 3 * (n_out + 8), &w));
   uint32_t *src = w, *is_spread = w + (n_out + 8), *before = w + 2 * (n_out + 8);
@@ -160,6 +168,15 @@ static int emit_merged(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t 
   if (ns) ELP_LAUNCH(groups, "merge_mark", k_merge_mark, dim3(blocks_for(ns, 256)), dim3(256), 0, ns, (const uint64_t *)slots, is_spread, src);
   ELP_TRY(exclusive_scan_u32(groups, is_spread, before, n_out, nullptr));
   ELP_LAUNCH(groups, "merge_fill", k_merge_fill, dim3(blocks_for(n_out, 256)), dim3(256), 0, n_out, (const uint32_t *)is_spread, (const uint32_t *)before, src);
+  *src_out = src;
+  return 0;
+}
+static int emit_merged(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out, OutFormat fmt, const char *who) {
+  if (!groups || !spread || groups == spread || !n_bytes_out) return ELP_ERR_ARG;
+  const uint32_t *src = nullptr;
+  uint64_t n_out = 0;
+  ELP_TRY(merged_list(groups, spread, fmt, who, &src, &n_out));
+  if (n_out == 0) { *n_bytes_out = 0; return 0; }
   return emit_two(groups, spread, src, n_out, out, cap, n_bytes_out, fmt, who);
 }
 
@@ -257,3 +274,13 @@ int elp_set_replace_read_group(elp_ctx *c, const uint8_t *id, int id_len) {
 }
 
 }  // extern "C"
+
+// for the index of the sorted and the merged stream (bai.hip; declared in bamout.hpp): what their emitters above work from
+namespace elp {
+uint64_t emit_out_growth(const elp_ctx *c) { return out_growth(c); }
+int emit_merged_list(elp_ctx *groups, elp_ctx *spread, const char *who, BamOut *mg, BamOut *ms, const uint32_t **src, uint64_t *n_out) {
+  ELP_TRY(merged_list(groups, spread, OutFormat::BGZF, who, src, n_out));
+  two_columns(groups, spread, mg, ms);
+  return 0;
+}
+}  // namespace elp

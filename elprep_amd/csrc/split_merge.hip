@@ -67,6 +67,22 @@ __global__ __launch_bounds__(MERGE_CHECK_W) void k_merge_check_order(uint64_t n_
   if (__ballot(inv) && (threadIdx.x & 63u) == 0) atomicOr(bad, 1u);
 }
 
+// The same check for ONE context that holds a plain keep permutation (the index of its stream, bai.hip): its n_out output records' keys
+// into `keys` (n_out entries of the caller's scratch), *in_order = none of them is smaller than the one in front.  Waits for the stream.
+int keep_coordinate_order(elp_ctx *c, uint64_t n_out, uint64_t *keys, uint32_t *bad_dev, bool *in_order) {
+  *in_order = true;
+  if (n_out < 2) return 0;
+  ELP_HIP(c, hipMemsetAsync(bad_dev, 0, 4, c->stream));
+  ELP_LAUNCH(c, "merge_keys", k_perm_keys, dim3(blocks_for(n_out, 256)), dim3(256), 0, n_out, (const uint32_t *)c->perm.p, (const int32_t *)c->refid.p,
+             (const int32_t *)c->pos.p, keys);
+  ELP_LAUNCH(c, "merge_check_order", k_merge_check_order, dim3(blocks_for(n_out, MERGE_CHECK_W)), dim3(MERGE_CHECK_W), 0, n_out, (const uint64_t *)keys, bad_dev);
+  uint32_t h_bad = 0;
+  ELP_HIP(c, hipMemcpyAsync(&h_bad, bad_dev, 4, hipMemcpyDeviceToHost, c->stream));
+  ELP_HIP(c, elp::stream_wait(c->stream));
+  *in_order = h_bad == 0;
+  return 0;
+}
+
 // MergeSortedFilesSplitPerChromosome's order as ranks, on the device: slots[j] = output slot of the j-th record of `spread`'s output
 // among `groups`' output (scratch slot 5 of `groups`; valid until that slot is reused).  Queued on groups->stream.
 // Either context holds a coordinate permutation or a plain keep permutation (elp_order_keep, by_split = 0): by choosing this call for

@@ -233,6 +233,25 @@ class Engine:
         """emit_concat_bam's stream as BGZF members (elp_emit_concat_bgzf)"""
         return self._emit_two(self.L.elp_emit_concat_bgzf, spread)
 
+    # ---- the BAM index of a stream just written (include/elprep_hip.h: SAM specification 5.2 on the device)
+    def _index(self, call) -> np.ndarray:
+        n = C.c_uint64()
+        self._check(call(C.c_void_p(0), 0, C.byref(n)))  # (exact)
+        out = np.empty(int(n.value), dtype=np.uint8)
+        self._check(call(_vp(out), out.size, C.byref(n)))
+        return out[:int(n.value)]
+
+    def index_sorted_bgzf(self, bgzf: np.ndarray, base_coffset: int = 0) -> np.ndarray:
+        """the .bai of the members emit_sorted_bgzf has just returned for this context as it is now (elp_index_sorted_bgzf); base_coffset:
+        the file offset at which the host writes them, behind its header blocks"""
+        bgzf = np.ascontiguousarray(bgzf, dtype=np.uint8)
+        return self._index(lambda out, cap, n: self.L.elp_index_sorted_bgzf(self.h, _vp(bgzf), bgzf.size, base_coffset, out, cap, n))
+
+    def index_merged_bgzf(self, spread: "Engine", bgzf: np.ndarray, base_coffset: int = 0) -> np.ndarray:
+        """the .bai of emit_merged_bgzf(spread)'s members (elp_index_merged_bgzf)"""
+        bgzf = np.ascontiguousarray(bgzf, dtype=np.uint8)
+        return self._index(lambda out, cap, n: self.L.elp_index_merged_bgzf(self.h, spread.h, _vp(bgzf), bgzf.size, base_coffset, out, cap, n))
+
     # ---- SAM text out (include/elprep_hip.h: FormatAlignment on the device)
     def _n_ref_in_force(self) -> int:
         n_ref = getattr(self, "_n_ref_now", None)  # (set by replace_reference_dictionary, until reset())

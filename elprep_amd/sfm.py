@@ -298,9 +298,10 @@ def emit_merged_device(groups, spread, part, group_of_ref: np.ndarray, n_groups:
     records (elp_stage_bam); `spread` is empty on every rank but the owner; `part` is an empty context of the same device group.
     order = "keep": `groups` and `spread` hold sorted input in input order (order_keep); `part`, which receives its reads in the spread
     file's order, is ordered the same way.
-    fmt = "sam": the stream as SAM lines without header text (elp_emit_merged_sam; the names are the header's ref_names)."""
-    if fmt not in ("bam", "sam"):
-        raise ValueError("fmt must be 'bam' or 'sam', not %r" % (fmt,))
+    fmt = "sam": the stream as SAM lines without header text (elp_emit_merged_sam; the names are the header's ref_names); "bgzf": as BGZF
+    members (elp_emit_merged_bgzf), which SfmRank.index_merged indexes."""
+    if fmt not in ("bam", "sam", "bgzf"):
+        raise ValueError("fmt must be 'bam', 'sam' or 'bgzf', not %r" % (fmt,))
     spread_owner = int(owner[n_groups + 1])
     part.reset()
     if rank == spread_owner and spread.n:
@@ -321,7 +322,7 @@ def emit_merged_device(groups, spread, part, group_of_ref: np.ndarray, n_groups:
             if send_to >= 0 or recv_from >= 0:
                 (spread if rank == spread_owner else part).exchange_records(send_to, idx, part if recv_from >= 0 else None, recv_from, new_split=0)
     _order_call(part, order)(False)
-    return groups.emit_merged_sam(part) if fmt == "sam" else groups.emit_merged_bam(part)
+    return {"sam": groups.emit_merged_sam, "bgzf": groups.emit_merged_bgzf, "bam": groups.emit_merged_bam}[fmt](part)
 
 
 # ------------------------------------------------------------------------------------------------ output order
@@ -593,7 +594,7 @@ class SfmRank:
         """the merge phase of this rank (emit_merged_device): the BAM records of its contig groups' output with the spread reads of those
         groups inserted - every context of the rank that sends or receives joins the device group first (the communicator the tables were
         reduced on, or the send-receive callback).  The records must have been staged from BAM bytes (route(..., stage=...)).  order: what
-        step() was given.  fmt: "bam" (records) or "sam" (lines, without header text)."""
+        step() was given.  fmt: "bam" (records), "sam" (lines, without header text) or "bgzf" (the records as BGZF members)."""
         from .engine import Engine
         if getattr(self, "_part", None) is None:
             self._part = Engine(self.header, self._device_ordinal)
@@ -607,6 +608,16 @@ class SfmRank:
                         e.group_init_transport(self.comm.rank, self.comm.world, lambda v: None)
                         e.group_set_p2p(self.comm.sendrecv)
         return emit_merged_device(self.engines[0], self.engines[1], self._part, group_of_ref, n_groups, owner, self.comm.rank, self.comm.world, order, fmt)
+
+    def index_merged(self, bgzf: np.ndarray, base_coffset: int = 0) -> np.ndarray:
+        """the .bai of the members emit_merged(..., fmt="bgzf") has just returned (elp_index_merged_bgzf), for the host that writes them at
+        file offset base_coffset.  A world of one: the rank's stream is the file.  With more ranks every rank's stream is a part of the
+        file, and joining the parts' indices is host arithmetic on offsets that is not done here."""
+        if self.comm.world != 1:
+            raise NotImplementedError("index_merged: joining the indices of several ranks' parts is the host's")
+        if getattr(self, "_part", None) is None:
+            raise ValueError("index_merged: call emit_merged(..., fmt='bgzf') first")
+        return self.engines[0].index_merged_bgzf(self._part, bgzf, base_coffset)
 
     def close(self):
         if self._side is not None:

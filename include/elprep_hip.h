@@ -225,6 +225,38 @@ int elp_emit_merged_bgzf(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_
 int elp_emit_concat_bam(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out);
 int elp_emit_concat_bgzf(elp_ctx *groups, elp_ctx *spread, uint8_t *out, uint64_t cap, uint64_t *n_bytes_out);
 
+/* ---- the BAM index of a stream the device has written (SAM specification 5.2; csrc/bai.hip, csrc/bai_plan.hpp) ----
+ * The reference writes no index: this is an extension.  elp_index_sorted_bgzf makes the .bai of the members elp_emit_sorted_bgzf has just
+ * returned, elp_index_merged_bgzf that of elp_emit_merged_bgzf's, from the context's columns and the members' sizes - nothing is inflated,
+ * no record comes back to the host.  `bgzf`, `n_bytes`: exactly what the emit call returned for the context(s) in their PRESENT state
+ * (permutation, tag filter, replacing read group, CleanSam); base_coffset: the file offset at which the host writes these members, behind
+ * its header block(s).  bai_out = NULL: a size query, exact.  The call invalidates nothing and writes only scratch and bai_out; a refused
+ * call writes nothing.
+ *   The host part (bai_plan.hpp) walks the members of the untrusted bytes - the 18-byte header 1f 8b 08 04 .. XLEN 6, 'B' 'C' 2 0,
+ * BSIZE at byte 16, ISIZE in the last four bytes; every member but the last holds 65280 bytes, the last 1 .. 65280; no members at all is
+ * valid - and gives coff[0 .. n_members], coff[n_members] = n_bytes.  ELP_ERR_DATA names the byte of a truncated member, a bad magic or
+ * subfield, a BSIZE that runs past the end, a wrong ISIZE.  The ISIZE must add up to the stream length the device's size pass finds for
+ * the context: else ELP_ERR_ARG "these bytes are not this context's stream".
+ *   The index, canonical.  Stream position p has the virtual offset voff(p) = (base_coffset + coff[p / 65280]) << 16 | p % 65280.  Output
+ * record k (the emitter's order and sizes): S = voff of its first byte, E = voff of the byte behind its last.  refid < 0: counted in
+ * n_no_coor and nothing else.  Otherwise beg = max(POS - 1, 0), end = beg + span, span = the reference-consuming operations of the CIGAR
+ * column as emitted, 1 if that is 0 or FLAG & 0x4; bin = reg2bin(beg, end - 1); windows beg >> 14 .. (end - 1) >> 14.
+ *   Bytes, little-endian: "BAI\1", int32 n_ref (the dictionary in force); per contig int32 n_bin, the bins, int32 n_intv, uint64
+ * ioffset[n_intv]; uint64 n_no_coor (always).  A contig without records: n_bin 0, n_intv 0.  With records: n_bin = distinct bins + 1, in
+ * ascending bin number, each uint32 bin, int32 n_chunk, chunks uint64 beg, end: of a bin's records in output order one extends the
+ * current chunk iff S >> 16 == chunk.end >> 16 (it starts in the member the chunk ends in), else opens one; chunk.end = E of its last
+ * record.  Last the pseudo-bin 37450 with two chunks: (S of the contig's first record, E of its last), (n_mapped, n_unmapped by FLAG &
+ * 0x4).  n_intv = the largest window a record of the contig touches + 1; ioffset[w] = the smallest S of the records that touch w, for a
+ * window nobody touches the value of the next touched one to its right.
+ *   Checks: the context holds a coordinate permutation (elp_sort_coordinate), or a plain keep permutation (elp_order_keep, by_split = 0)
+ * whose (refid, POS) order passes elp_merge_spread's check - else ELP_ERR_DATA "records are not in coordinate order".  A queryname or
+ * by-split permutation, none at all, records not staged with elp_stage_bam / _bgzf / _sam, cap below the size, base_coffset + n_bytes
+ * beyond 2^48: ELP_ERR_ARG.  A record that ends beyond position 2^29 (a bin cannot hold it): ELP_ERR_UNSUPPORTED.  The merged form runs
+ * elp_emit_merged_bam's checks.  Joining the indices of several ranks' parts of one file is host arithmetic on offsets, not done here. */
+int elp_index_sorted_bgzf(elp_ctx *ctx, const uint8_t *bgzf, uint64_t n_bytes, uint64_t base_coffset, uint8_t *bai_out, uint64_t cap, uint64_t *n_bytes_out);
+int elp_index_merged_bgzf(elp_ctx *groups, elp_ctx *spread, const uint8_t *bgzf, uint64_t n_bytes, uint64_t base_coffset, uint8_t *bai_out, uint64_t cap,
+                          uint64_t *n_bytes_out);
+
 /* ---- SAM text out (sam/sam-files.go:485-598; csrc/sam.hip) ----
  * The writer of the reference picks the format by the file's extension (sam/aln-files.go:134-135): these are the ".sam" forms of the
  * emitters above.  Each writes FormatAlignment(parseBamAlignment(record)) (:563-598, sam/bam-files.go:317-400) of every record its BAM
