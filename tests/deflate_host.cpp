@@ -10,6 +10,11 @@
 
 using namespace elp::dfl;
 
+// the three sizes the last dfl_emulate_block chose among: with fixed codes, with dynamic codes, stored (tests/bgzf_payloads.py: by how
+// many bytes the chosen form beat the others)
+static uint32_t g_sizes[3];
+extern "C" void dfl_last_sizes(uint32_t *out) { for (int k = 0; k < 3; k++) out[k] = g_sizes[k]; }
+
 // in: n <= PAYLOAD bytes; out: the block's DEFLATE data (cap >= n + 5 + 8).  Returns its size; *stored = 1 if the block was stored, 2 if it
 // has dynamic codes, 0 fixed codes.
 // order 0: the threads of a strip / the parts run in index order; 1: in reverse order (another legal schedule: the result must inflate too)
@@ -85,6 +90,9 @@ extern "C" uint32_t dfl_emulate_block(const uint8_t *in_bytes, uint32_t n, uint8
   }
   for (int p = 0; p < NT; p++) { doff[p] = (uint32_t)dtotal; dtotal += dbits[p]; }
   const uint32_t dyn_bytes = deflate_bytes_dyn(D, dtotal);
+  g_sizes[0] = deflate_bytes(total);
+  g_sizes[1] = dyn_bytes;
+  g_sizes[2] = n + 5u;
   const bool dynamic = mode != 1 && dyn_bytes < deflate_bytes(total);
   const uint32_t cbytes = dynamic ? dyn_bytes : deflate_bytes(total);
   if (cbytes >= n + 5u) {

@@ -13,8 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SO = os.path.join(ROOT, "tests", "libdeflate_host.so")
 
 
-@pytest.fixture(scope="module")
-def lib():
+def _build_lib():
+    """the host emulation, compiled where it is older than its sources (tests/bgzf_payloads.py loads it through here too)"""
     src = os.path.join(ROOT, "tests", "deflate_host.cpp")
     hdr = os.path.join(ROOT, "elprep_amd", "csrc", "deflate_core.hpp")
     if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
@@ -23,6 +23,11 @@ def lib():
     L.dfl_emulate_block.restype = C.c_uint32
     L.dfl_emulate_block.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]
     return L
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return _build_lib()
 
 
 def _deflate(L, data: bytes, order: int):
@@ -80,9 +85,8 @@ def test_every_block_inflates_to_its_payload(lib, order):
         assert len(cdata) >= 0 and ratios["bam block"][0] * len(data) < len(z.compress(data) + z.flush())
 
 
-def test_dynamic_codes_at_the_edges(lib):
-    """alphabets of one and two symbols, no distance code at all, a count distribution that wants codes longer than 15 bits (Fibonacci
-    counts: the length limit's repair), long runs of unused symbols (run-length symbols 17 and 18 of the header) - every block inflates"""
+def _edge_cases():
+    """the payloads of test_dynamic_codes_at_the_edges (tests/bgzf_payloads.py takes them into its catalogue)"""
     rng = np.random.default_rng(5)
     fib = [1, 1]
     while sum(fib) < 40000:
@@ -98,6 +102,13 @@ def test_dynamic_codes_at_the_edges(lib):
         "two values": bytes(rng.integers(0, 2, 65280, dtype=np.uint8) * 255),
         "sparse alphabet": bytes(rng.choice(np.array([0, 1, 2, 127, 128, 254, 255], dtype=np.uint8), 30000)),
     }
+    return cases
+
+
+def test_dynamic_codes_at_the_edges(lib):
+    """alphabets of one and two symbols, no distance code at all, a count distribution that wants codes longer than 15 bits (Fibonacci
+    counts: the length limit's repair), long runs of unused symbols (run-length symbols 17 and 18 of the header) - every block inflates"""
+    cases = _edge_cases()
     kinds = {}
     for name, data in cases.items():
         for order in (0, 1):
@@ -114,7 +125,8 @@ def test_symbol_tables_against_the_rfc(lib):
     base = rng.integers(0, 256, 70000, dtype=np.uint8).tobytes()
     seen = set()
     for dist in [1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 16, 17, 24, 25, 32, 33, 48, 49, 64, 65, 96, 97, 128, 129, 192, 193, 256, 257, 384, 385, 512, 513, 768, 769, 1024,
-                 1025, 1536, 1537, 2048, 2049, 3072, 3073, 4096, 4097, 6144, 6145, 8192, 8193, 12288, 12289, 16384, 16385, 24576, 24577, 32767, 32768]:
+                 1025, 1536, 1537, 2048, 2049, 3072, 3073, 4096, 4097, 6144, 6145, 8192, 8193, 12288, 12289, 16384, 16385, 24576, 24577, 32767, 32768,
+                 32769, 32770, 33000]:  # (beyond the window: the copy goes out as literals.  tests/bgzf_payloads.py holds the tokens to that)
         for length in (4, 5, 10, 11, 12, 13, 18, 19, 34, 35, 66, 67, 115, 130, 131, 226, 227, 250, 254):
             k = max((dist + 255) // 256, 1)       # the copy starts strip k, i.e. at offset k of part k
             if k + length > 255:
