@@ -2,7 +2,7 @@
 //
 // Reference: BaseRecalibratorTables.ApplyBQSR (filters/bqsr.go:936-1005): every base with quality >= 6 of a record whose read group is
 // in the tables is replaced by the memo value of (read group, quality, cycle, context); cycle and context are taken on the full,
-// unclipped read.  Same bytes as k_bqsr_apply_flat (bqsr_apply.hip), which stays as the general kernel (ragged lengths, reads longer than
+// unclipped read.  Same bytes as k_bqsr_apply_flat (apply_flat.hip), which stays as the general kernel (ragged lengths, reads longer than
 // --max-cycle, LUTs with more than ~250 distinct rows).
 //
 //   - A workgroup trip covers RPI = 1024 / (blocks per read) whole reads; lane t is block t % bpr of read slot t / bpr for the whole
@@ -27,8 +27,7 @@
 namespace elp {
 
 constexpr uint32_t A3_N1 = 0x11111111u, A3_C3 = 0x33333333u;
-// (A3_ROW, the bytes between two level-2 rows in LDS: bqsr_plan.hpp)
-constexpr int A3_NT = 512;  // three workgroups per CU around three copies of the LUT (~50 KB each): six waves per SIMD
+// (A3_ROW, the bytes between two level-2 rows in LDS, A3_NT, A3_MAXCOV, A3_RBLOCKS: apply_plan.hpp)
 __global__ __launch_bounds__(256) void k_apply_records(uint64_t n, uint32_t len, int lmax, const uint16_t *__restrict__ flag, const uint16_t *__restrict__ rgid,
                                                        const uint16_t *__restrict__ rg_cov, const uint64_t *__restrict__ qbounds,
                                                        const uint8_t *__restrict__ cov_present, uint2 *__restrict__ recs, uint32_t *err) {
@@ -50,7 +49,7 @@ __global__ __launch_bounds__(256) void k_apply_records(uint64_t n, uint32_t len,
 // LUT has more distinct rows than one-byte ids hold): only the reads ApplyBQSR touches get a record, the records of one covariate lie
 // together (counts per covariate, offsets, a scatter: the shape of k_c3_other_* in bqsr_count.hip), the read's staging index next to the
 // record; a workgroup of k_bqsr_apply3<true> then holds ONE covariate's level 1 and that covariate's own row dictionary at a time.
-constexpr int A3_MAXCOV = 256, A3_RTILE = 1024;
+constexpr int A3_RTILE = 1024;
 __device__ __forceinline__ int apply_read_cov(uint16_t rg, const uint16_t *__restrict__ rg_cov, const uint8_t *__restrict__ cov_present, uint32_t *err) {
   if (rg == ELP_NIL16) { if (err) atomicOr(&err[0], 32u); return -1; }
   const uint32_t cov = rg_cov[rg] & 0xFFu;
@@ -59,7 +58,6 @@ __device__ __forceinline__ int apply_read_cov(uint16_t rg, const uint16_t *__res
 // Both passes run the SAME few workgroups over the same chunks of tiles (workgroup b: tiles [b * per, (b + 1) * per)): the counters all
 // workgroups add to share one cache line, and a line takes about one atomic per clock - with a workgroup per tile (15 700 of them at
 // 16 M reads, 16 to 32 counters each) those flushes were the two kernels' time (0.19 + 0.21 ms; 0.03 of it the loads).
-constexpr int A3_RBLOCKS = 1024;
 __global__ __launch_bounds__(256) void k_apply_cov_hist(uint64_t n, uint32_t per, const uint16_t *__restrict__ rgid, const uint16_t *__restrict__ rg_cov,
                                                         const uint8_t *__restrict__ cov_present, uint32_t *__restrict__ cnt /* [A3_MAXCOV] */,
                                                         uint32_t *__restrict__ blk /* [gridDim.x][A3_MAXCOV] */, uint32_t *err) {
@@ -262,12 +260,12 @@ struct Apply3 {
   }
 };
 
-// The static LDS apply3_bytes (bqsr_plan.hpp) and apply3_launch set aside for k_bqsr_apply3: the kernel's __shared__ arrays, term by term (the
+// The static LDS apply3_bytes and Apply3Launch (apply_plan.hpp) set aside for k_bqsr_apply3: the kernel's __shared__ arrays, term by term (the
 // kernel asserts the sums against its own declarations), and a margin.  The covariate split's prefix-sum arrays come on top in its launch only.
 constexpr size_t APPLY3_LDS_ARRAYS = sizeof(uint8_t[A3_MAXCOV]);
 constexpr size_t APPLY3_LDS_ARRAYS_SPLIT = sizeof(uint32_t[A3_MAXCOV]) + sizeof(uint32_t[A3_MAXCOV + 1]) + sizeof(uint32_t[4]);
 constexpr size_t APPLY3_LDS = APPLY3_LDS_ARRAYS + 256, APPLY3_LDS_SPLIT = APPLY3_LDS_ARRAYS_SPLIT + 236;
-extern const size_t APPLY3_STATIC_LDS = APPLY3_LDS;
+extern const size_t APPLY3_STATIC_LDS = APPLY3_LDS, APPLY3_STATIC_LDS_SPLIT = APPLY3_LDS_SPLIT;
 static_assert(APPLY3_LDS == 512 && APPLY3_LDS_SPLIT == 2304, "the budgets the plan was written around");
 
 template <bool SPLIT>
@@ -475,31 +473,20 @@ __global__ __launch_bounds__(A3_NT, 6) void k_bqsr_apply3(Apply3Args A) {  // si
 int apply3_launch(elp_ctx *c, int max_cycle, const uint8_t *d_lut, const uint8_t *d_cov_present, const uint16_t *t1, const uint8_t *t2, const uint32_t *n_dict_dev,
                   int n_qi, int lmax, size_t dyn, bool split) {
   const uint64_t n = c->n;
-  const uint32_t len = c->uniform_len, bpr = (len + 15u) >> 4;
-  // reads packed over the whole workgroup unless that puts the last two blocks of some read (which overlap when the length is not a
-  // multiple of 16) into different waves: then whole reads per wave
-  uint32_t group = A3_NT;
-  if ((len & 15u) && bpr > 1)
-    for (uint32_t slot = 0; slot < A3_NT / bpr; slot++)
-      if (((slot * bpr + bpr - 1u) & 63u) == 0) group = 64;
-  const uint32_t rpi = (group / bpr) * (A3_NT / group);
-  unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(3, LDS_CU / (dyn + APPLY3_LDS + (split ? APPLY3_LDS_SPLIT : 0))));
-  if (c->tune.apply_wgs >= 1 && c->tune.apply_wgs <= 3) per_cu = std::min(per_cu, (unsigned)c->tune.apply_wgs);
-  const int grid = (int)std::min<uint64_t>((n + rpi - 1) / rpi, (uint64_t)c->n_cu * per_cu);
-  uint2 *recs;
-  const size_t dump_words = (size_t)grid * A3_NT * 2;  // 16 bytes per lane, in uint2 units
-  // records | dump | (split) staging indices | counts per covariate, offsets, cursors
-  const size_t rec_words = (n + 4 + 1) & ~(uint64_t)1;
-  ELP_TRY(scratch(c, 5, rec_words + dump_words + (split ? (n + 1) / 2 + 2 * A3_MAXCOV + 8 + (size_t)A3_RBLOCKS * A3_MAXCOV / 2 : 0) + 8, &recs));
-  uint8_t *dump = reinterpret_cast<uint8_t *>(recs + rec_words);
-  uint32_t *ridx = reinterpret_cast<uint32_t *>(recs + rec_words + dump_words), *cw = ridx + ((n + 1) & ~(uint64_t)1);  // cw: [256] counts | [257] offsets | [256] cursors
+  const uint32_t len = c->uniform_len;
+  const Apply3Launch P(n, len, c->n_cu, dyn, split, c->tune.apply_wgs, APPLY3_LDS, APPLY3_LDS_SPLIT);
+  uint8_t *slot5;
+  ELP_TRY(scratch(c, 5, P.size8 * 8, &slot5));
+  uint2 *recs = reinterpret_cast<uint2 *>(slot5 + P.recs);
+  uint8_t *dump = slot5 + P.dump;
+  uint32_t *ridx = reinterpret_cast<uint32_t *>(slot5 + P.ridx), *cw = reinterpret_cast<uint32_t *>(slot5 + P.cw);  // cw: [256] counts | [257] offsets | [256] cursors
   if (split) {
     ELP_HIP(c, hipMemsetAsync(cw, 0, (3 * A3_MAXCOV + 1) * sizeof(uint32_t), c->stream));
-    // cw: ... | [A3_RBLOCKS][256] the workgroups' counts (written whole by the first pass)
+    // blk: [A3_RBLOCKS][256] the workgroups' counts (written whole by the first pass)
     const uint64_t tiles = blocks_for(n, A3_RTILE);
     const unsigned rg = (unsigned)std::min<uint64_t>(tiles, A3_RBLOCKS);
     const uint32_t per = (uint32_t)((tiles + rg - 1) / rg);
-    uint32_t *blk = cw + 3 * A3_MAXCOV + 8;
+    uint32_t *blk = reinterpret_cast<uint32_t *>(slot5 + P.blk);
     ELP_LAUNCH(c, "bqsr_apply_cov_hist", k_apply_cov_hist, dim3(rg), dim3(256), 0, n, per, (const uint16_t *)c->rgid.p, (const uint16_t *)c->rg_cov.p, d_cov_present, cw, blk,
                c->err_flag.p);
     ELP_LAUNCH(c, "bqsr_apply_cov_offsets", k_apply_cov_offsets, dim3(1), dim3(1), 0, (const uint32_t *)cw, cw + A3_MAXCOV, cw + 2 * A3_MAXCOV + 1);
@@ -512,14 +499,10 @@ int apply3_launch(elp_ctx *c, int max_cycle, const uint8_t *d_lut, const uint8_t
     ELP_LAUNCH(c, "bqsr_apply_records", k_apply_records, dim3(blocks_for(n, 256)), dim3(256), 0, n, len, lmax, (const uint16_t *)c->flag.p,
                (const uint16_t *)c->rgid.p, (const uint16_t *)c->rg_cov.p, (const uint64_t *)c->qbounds.p, d_cov_present, recs, c->err_flag.p);
   Apply3Args A{n, len, c->qual.p, c->seq4.p + elp_ctx::SEQ_FRONT, adapt_recs ? (const uint2 *)c->apply_recs.p : (const uint2 *)recs, d_lut, t1, t2, n_dict_dev, c->n_cov, n_qi,
-               lmax, max_cycle, c->err_flag.p, dump, group, ridx, cw, cw + A3_MAXCOV, adapt_recs ? d_cov_present : (const uint8_t *)nullptr};
-  if (split) {
-    ELP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bqsr_apply3<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    ELP_LAUNCH(c, "bqsr_apply", k_bqsr_apply3<true>, dim3(grid), dim3(A3_NT), dyn, A);
-  } else {
-    ELP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bqsr_apply3<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    ELP_LAUNCH(c, "bqsr_apply", k_bqsr_apply3<false>, dim3(grid), dim3(A3_NT), dyn, A);
-  }
+               lmax, max_cycle, c->err_flag.p, dump, P.group, ridx, cw, cw + A3_MAXCOV, adapt_recs ? d_cov_present : (const uint8_t *)nullptr};
+  void (*const k)(Apply3Args) = split ? k_bqsr_apply3<true> : k_bqsr_apply3<false>;
+  ELP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+  ELP_LAUNCH(c, "bqsr_apply", k, dim3(P.grid), dim3(A3_NT), dyn, A);
   return 0;
 }
 

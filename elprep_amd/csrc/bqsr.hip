@@ -9,7 +9,7 @@
 //                               (bqsr_count.hip), the error word, and the retry with the exact quality set when the sampled hint missed one
 //   the tables' way back        elp_bqsr_tables_fetch, elp_bqsr_tables_fetch_rows (k_tables_pack_rows), elp_bqsr_quals_counted
 //   bqsr_error                  the device error word as the call's error, for this file and bqsr_apply.hip
-// ApplyBQSR is in bqsr_apply.hip and apply3.hip.
+// ApplyBQSR is in bqsr_apply.hip, bqsr_lut.hip, apply_flat.hip and apply3.hip.
 #include <utility>
 
 #include "bqsr_common.hpp"

@@ -1,8 +1,10 @@
 // bqsr_common.hpp — what the BQSR translation units share: the per-record descriptor the prologue kernels leave for the count
 // kernels, the 4-bit packed reference windows, LDS atomics and the one-instruction helpers, and the functions by which the stage's
 // translation units call each other: bqsr.hip (reference, known sites, the gather's host side, table fetches) -> bqsr_prologue.hip,
-// bqsr_count.hip, count3.hip; bqsr_apply.hip -> apply3.hip.  The launch plans are host arithmetic of their own (bqsr_plan.hpp).
+// bqsr_count.hip, count3.hip; bqsr_apply.hip (elp_bqsr_apply's chain of forms) -> bqsr_lut.hip (the LUT's upload, its row dictionary),
+// apply3.hip, apply_flat.hip.  The launch plans are host arithmetic of their own (bqsr_plan.hpp, apply_plan.hpp).
 #pragma once
+#include "apply_plan.hpp"
 #include "bqsr_dev.hpp"
 #include "bqsr_plan.hpp"
 #include "flat.hpp"
@@ -357,15 +359,26 @@ struct PrologueBufs {
 };
 int prologue_launch(elp_ctx *c, const PrologueBufs &b, const GatherScratch &S, const RecOut &ro);
 
-// ---- static LDS of the kernels the plans of bqsr_plan.hpp budget for, each defined beside its kernel's __shared__ declarations
+// ---- static LDS of the kernels the plans of bqsr_plan.hpp and apply_plan.hpp budget for, each defined beside its kernel's __shared__ declarations
 extern const size_t COUNT3_STATIC_LDS;                        // count3.hip: k_bqsr_count3
 extern const size_t COUNT_STATIC_LDS, COUNT_STATIC_LDS_1024;  // bqsr_count.hip: k_bqsr_count with 512 / 1024 threads
-extern const size_t APPLY3_STATIC_LDS;                        // apply3.hip: k_bqsr_apply3
+extern const size_t APPLY3_STATIC_LDS, APPLY3_STATIC_LDS_SPLIT;  // apply3.hip: k_bqsr_apply3, and what its covariate split adds
+extern const size_t APPLY_STATIC_LDS;                         // apply_flat.hip: k_bqsr_apply_flat
 
 int bqsr_error(elp_ctx *c, uint32_t e);  // bqsr.hip: the device error word as the call's error
 
-// ---- ApplyBQSR for read sets of one length (apply3.hip)
+// ---- ApplyBQSR: the plan's inputs and the row dictionary (bqsr_lut.hip), the kernels' launches (apply3.hip, apply_flat.hip)
+ApplyShape apply_shape(const elp_ctx *c, int max_cycle);
+// the dictionary's regions (apply_plan.hpp: LutDictLayout) in the block at wk
+struct LutDict { uint32_t *slots, *slot_id, *row_slot, *counter; uint16_t *t1; uint8_t *t2; uint32_t n_slots; size_t n_rows, n1; };
+inline LutDict lut_dict_at(uint32_t *wk, const LutDictLayout &L) {
+  return LutDict{wk + L.slots, wk + L.slot_id, wk + L.row_slot, wk + L.counter, reinterpret_cast<uint16_t *>(wk + L.t1), reinterpret_cast<uint8_t *>(wk + L.t2), L.n_slots, L.n_rows, L.n1};
+}
+int lut_dict_build(elp_ctx *c, hipStream_t st, const LutDict &D, const uint8_t *dl, int qlo, int n_qi, int lmax, int max_cycle, bool per_cov);
 int apply3_launch(elp_ctx *c, int max_cycle, const uint8_t *d_lut, const uint8_t *d_cov_present, const uint16_t *t1, const uint8_t *t2, const uint32_t *n_dict_dev,
                   int n_qi, int lmax, size_t dyn, bool split /* records sorted by covariate, per-covariate row dictionaries */);
+// n_dict: distinct rows of the one dictionary at t1 / t2, NO_DICT if there is none
+int apply_flat_launch(elp_ctx *c, const ApplyShape &s, const ApplyPlan &p, const uint8_t *d_lut, const uint8_t *d_cov_present, const uint16_t *t1, const uint8_t *t2,
+                      uint32_t n_dict);
 
 }  // namespace elp

@@ -9,7 +9,7 @@
 // Float finalisation (FinalizeBQSRTables, the hierarchical Bayesian estimate) is host work; the device consumes its result
 // as a dense byte LUT.
 //
-// Per-base covariates are local functions of the read (evaluated block-wise in bqsr_count.hip, bqsr_apply.hip / flat.hpp):
+// Per-base covariates are local functions of the read (evaluated block-wise in bqsr_count.hip, apply_flat.hip / flat.hpp):
 //   cycle(k)   = cycleFactor + k * increment                                   (bqsr.go:376-387)
 //   context(k) = 2-mer key of (previous, current) base in sequencing direction, -1 at the first sequenced base, next to a
 //                non-ACGT base, or inside the low-quality tails (quality <= 2 from either end)   (bqsr.go:87-146, 312-362)

@@ -23,7 +23,6 @@ constexpr int C3_CSTRIDE = 64;  // words between two counters: every counter in 
 // k_c3_seg_hist walks the RGID column in the same workgroups to size the covariate-split segments exactly
 constexpr int PF_TILES = 16;
 constexpr int CO_MAXCOV = 256;  // covariates the other region's sort handles (a covariate id is a byte: any number of read groups the context accepts)
-constexpr int A3_ROW = 20;  // apply3.hip: bytes between two level-2 rows in LDS (17 used)
 
 // ---- the one-length count kernel (count3.hip): one workgroup of 1024 threads per CU around one table; the context cells are replicated
 // as often as the CU's LDS allows.  Returns 1 if the tables of this pass do not fit (the caller uses k_bqsr_count).
@@ -40,15 +39,6 @@ inline int count3_plan(int n_cov, int n_q, int lmax, size_t static_lds, int *rsw
     }
   }
   return 1;
-}
-
-// ---- ApplyBQSR for read sets of one length (apply3.hip).  LDS of a launch: level 1 + room for 256 level-2 rows (their number is not read
-// back in front of the launch); 1 = does not fit
-inline int apply3_bytes(int n_cov, int n_qi, int lmax, size_t static_lds, size_t *dyn_out) {
-  const size_t n1 = (size_t)n_cov * (size_t)(6 + n_qi + 1) * (size_t)(2 * lmax + 1);
-  const size_t dyn = ((n1 + 15) & ~(size_t)15) + (size_t)256 * A3_ROW + 16;
-  *dyn_out = dyn;
-  return dyn + static_lds <= LDS_CU ? 0 : 1;
 }
 
 // ---- the gather: what decides the plan besides the number of quality slots
@@ -159,3 +149,6 @@ struct GatherScratch {
 };
 
 }  // namespace elp
+
+// ApplyBQSR's plans are a header of their own; whoever includes this one has them too (apply3_bytes lived here before)
+#include "apply_plan.hpp"

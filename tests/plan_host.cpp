@@ -23,14 +23,6 @@ int plan_count3(int n_cov, int nq, int lmax, uint64_t static_lds, int force_rlog
   return rc;
 }
 
-// out: dyn; returns 1 if it does not fit
-int plan_apply3(int n_cov, int n_qi, int lmax, uint64_t static_lds, uint64_t *out) {
-  size_t dyn = 0;
-  const int rc = apply3_bytes(n_cov, n_qi, lmax, (size_t)static_lds, &dyn);
-  out[0] = (uint64_t)dyn;
-  return rc;
-}
-
 // out: fits, wg_per_cu, big, mg, rs, ncp, qcap, passes, dyn of a full pass (ncp covariates x min(qcap, nq) slots)
 void plan_general(int n_cov, int nq, int lmax, const uint64_t *lds, int64_t *out) {
   const CountPlan p = count_general_plan(shape(n_cov, lmax, 0, 0, 0, -1, lds), nq);

@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SO = os.path.join(ROOT, "tests", "libplan_host.so")
 
 LDS_CU = 160 * 1024
-L3, L512, L1024, LA3 = 4480, 18872, 32184, 512
+L3, L512, L1024 = 4480, 18872, 32184
 LMAXS = (1, 16, 17, 100, 150, 151, 250, 1022, 1023)
 GENERAL = ("fits", "wg_per_cu", "big", "mg", "rs", "ncp", "qcap", "passes", "dyn")
 
@@ -240,10 +240,3 @@ def test_gather_scratch_layout(lib, n):
     assert (other1, slots1) == (64 * cap_s1, 64 * cap_s1 + n + 64)
     assert (other2, slots2) == (n, 3 * n + 64)  # covariate split: exact segments | the other region | the other region sorted
 
-
-def test_apply3_bytes(lib):
-    """4 read groups, qualities 6 .. 45 (40 resident), 150 bases: level 1 = 4 * (6 + 40 + 1) * 301 = 56588 bytes -> 56592, + 256 rows of 20 bytes
-    + 16 = 61728; fits (+ 512 static).  16 read groups: 226352 bytes of level 1 alone do not."""
-    out = (C.c_uint64 * 1)()
-    assert lib.plan_apply3(4, 40, 150, C.c_uint64(LA3), out) == 0 and out[0] == 61728
-    assert lib.plan_apply3(16, 40, 150, C.c_uint64(LA3), out) == 1

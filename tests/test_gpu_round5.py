@@ -3,6 +3,7 @@ any number of read groups in BQSR gather and apply (the reference's tables are m
 the general count kernel in passes over covariate subsets, the one-length count kernel on exactly-sized per-covariate segments with its
 trips shared evenly among the workgroups, ApplyBQSR split by covariate with one row dictionary per covariate."""
 import dataclasses
+import functools
 
 import numpy as np
 import pytest
@@ -117,27 +118,61 @@ def _random_tables(h, quals, max_cycle, length, seed, spread):
     return qt, ct, xt
 
 
-@pytest.mark.parametrize("n_q,expect", [(3, "per covariate"), (14, "general")])
-def test_apply_with_more_distinct_lut_rows_than_one_dictionary_holds(n_q, expect):
-    """a LUT whose rows are (nearly) all distinct: the one dictionary of ApplyBQSR's one-length kernel overflows its one-byte ids, the
-    kernel leaves without touching a byte and the host takes one dictionary per covariate - or, if a covariate's rows do not fit
-    either, the general kernel; the bytes are the oracle's ApplyBQSR on the same tables each time"""
+@functools.lru_cache(maxsize=None)
+def _many_rows_case(n_q):
+    """5000 reads of 120 bases in 4 read groups and tables whose LUT has (nearly) only distinct rows; the oracle's ApplyBQSR on them"""
     quals = [2] + [6 + 3 * k for k in range(n_q)]
     b, h, refs, sites = _uniform_case(55, 5000, 120, quals=quals, n_cov=4)
     qt, ct, xt = _random_tables(h, quals[1:], 500, 120, 9, 0.5)
     want = orc.BqsrFinal(qt, ct, xt, 500).apply(b, h, 0)
-    lut, present = BqsrTables(qt, ct, xt, 500).finalize().build_lut(0)
+    tb = BqsrTables(qt, ct, xt, 500).finalize()
+    lut, present = tb.build_lut(0)
+    return quals, b, h, refs, sites, want, lut, present, tb.build_lut_rows(quals[1:], 0)
+
+
+@pytest.mark.parametrize("n_q,expect", [(3, "per covariate"), (14, "general")])
+@pytest.mark.parametrize("arrives", ["call", "upload", "upload_rows"])
+def test_apply_with_more_distinct_lut_rows_than_one_dictionary_holds(arrives, n_q, expect):
+    """a LUT whose rows are (nearly) all distinct: the one dictionary of ApplyBQSR's one-length kernel overflows its one-byte ids, the
+    kernel leaves without touching a byte and the host takes one dictionary per covariate - or, if a covariate's rows do not fit
+    either, the general kernel; the bytes are the oracle's ApplyBQSR on the same tables each time.  The LUT comes with the call, or
+    (the benchmark's path) is uploaded ahead, dense or in rows form, behind a gather that left the quality hint and the one-length
+    fact - the dictionary is then built behind the upload on the copy stream, and the overflow meets that one; a second upload and apply
+    on the rolled-back context finds the first apply's dictionary of the other form in place.  With the default tuning every apply call
+    launches the apply kernel twice ("per covariate": the overflowed one dictionary, then one per covariate) or three times ("general":
+    both one-length forms overflow, then the general kernel)."""
+    quals, b, h, refs, sites, want, lut, present, rows_form = _many_rows_case(n_q)
     rows = lut.reshape(h.n_cov, 94, 1001, 17)[:, quals[1:], 500 - 120:500 + 121]
     n_all = len({r.tobytes() for r in rows.reshape(-1, 17)})
     n_per = max(len({r.tobytes() for r in rows[c].reshape(-1, 17)}) for c in range(h.n_cov))
     assert n_all > 249
     assert (n_per <= 249) == (expect == "per covariate"), (n_all, n_per)
+    launches = {"per covariate": 2, "general": 3}[expect]
     for tune in ({}, {"apply_kernel": 3}, {"apply_kernel": 1}):
         e = Engine(h, tuning=tune)
         e.stage(b)
-        got = e.apply_bqsr(lut, present, 500)
+        e.profile_enable(True)
+        if arrives == "call":
+            got = e.apply_bqsr(lut, present, 500)
+            assert np.array_equal(got, want), tune
+            assert tune or e.profile()["bqsr_apply"][0] == launches, (tune, e.profile())
+        else:
+            for r in range(h.n_ref):
+                e.set_reference(r, refs[r])
+                e.set_known_sites(r, sites[r])
+            e.recalibrate(500)  # (QUAL is not touched: `want` stands)
+            e.snapshot()
+            for attempt in range(2):
+                if arrives == "upload":
+                    e.lut_upload(lut, present, 500)
+                else:
+                    e.lut_upload_rows(quals[1:], *rows_form, 500)
+                e.profile_reset()
+                got = e.apply_bqsr(None, None, 500)
+                assert np.array_equal(got, want), (tune, attempt)
+                assert tune or e.profile()["bqsr_apply"][0] == launches, (tune, attempt, e.profile())
+                e.rollback()
         e.close()
-        assert np.array_equal(got, want), tune
 
 
 def test_genome_with_hg38_sized_contigs():
