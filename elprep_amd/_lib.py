@@ -33,6 +33,7 @@ HIP_SYMBOLS = [
     "elp_set_reference_names_flat", "elp_emit_sorted_sam", "elp_emit_merged_sam", "elp_emit_concat_sam", "elp_stage_sam",
     "elp_emit_split_bam", "elp_emit_split_bgzf", "elp_emit_split_sam",
     "elp_index_sorted_bgzf", "elp_index_merged_bgzf",
+    "elp_sw_align", "elp_sw_align_reads",
     "elp_snapshot", "elp_rollback", "elp_set_tuning", "elp_profile_enable", "elp_profile_reset", "elp_profile_count", "elp_profile_get", "elp_debug_check_guards",
 ]
 HOST_SYMBOLS = [
@@ -153,6 +154,13 @@ def hip() -> C.CDLL:
         # (an older build named by ELP_HIP_SO for A/B timing lacks the index calls; calling one of them there fails with AttributeError)
         for name, args in (("elp_index_sorted_bgzf", [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
                            ("elp_index_merged_bgzf", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)])):
+            if ELP_AB_BUILD and not hasattr(L, name):
+                continue
+            getattr(L, name).argtypes = args
+        # (an older build named by ELP_HIP_SO for A/B timing lacks the Smith-Waterman calls; calling one of them there fails with AttributeError)
+        sw_tail = [C.c_int32] * 4 + [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        for name, args in (("elp_sw_align", [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p] + sw_tail),
+                           ("elp_sw_align_reads", [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p] + sw_tail)):
             if ELP_AB_BUILD and not hasattr(L, name):
                 continue
             getattr(L, name).argtypes = args

@@ -285,6 +285,8 @@ struct elp_ctx {
                                // keep every CU partly occupied)
     int side_priority = 0;     // 1: the side lanes' streams are made with the highest priority the device offers (default: the default priority;
                                // measured with the bench's step: no difference)
+    long long sw_scratch_bytes = 0;  // > 0: elp_sw_align runs its listed problems in chunks of at most this much scratch (default 1 GiB,
+                                     // sw_plan.hpp; tests: several chunks on a small batch)
   } tune;
 
   // generic scratch pool (grown on demand, reused between calls)

@@ -650,6 +650,7 @@ int elp_set_tuning(elp_ctx *c, const char *key, int64_t value) {
   else if (k == "presort_tile") c->tune.presort_tile = v;
   else if (k == "count3_grid") { if (value < 0) return set_error(c, ELP_ERR_ARG, "elp_set_tuning: count3_grid must not be negative"); c->tune.count3_grid = v; }
   else if (k == "side_priority") c->tune.side_priority = v;
+  else if (k == "sw_scratch_bytes") { if (value < 0) return set_error(c, ELP_ERR_ARG, "elp_set_tuning: sw_scratch_bytes must not be negative"); c->tune.sw_scratch_bytes = value; }
   else return set_error(c, ELP_ERR_ARG, "elp_set_tuning: unknown key '%s'", key);
   return 0;
 }

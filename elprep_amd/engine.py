@@ -252,6 +252,61 @@ class Engine:
         bgzf = np.ascontiguousarray(bgzf, dtype=np.uint8)
         return self._index(lambda out, cap, n: self.L.elp_index_merged_bgzf(self.h, spread.h, _vp(bgzf), bgzf.size, base_coffset, out, cap, n))
 
+    # ---- the HaplotypeCaller's Smith-Waterman (include/elprep_hip.h: runSmithWaterman on the device)
+    @staticmethod
+    def _sw_pool(pool):
+        """a pool as a list of bytes, or as (bytes, off): (uint8 array, uint64 offsets, number of sequences)"""
+        if isinstance(pool, tuple):
+            data, off = pool
+            data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, dtype=np.uint8)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+        else:
+            data = np.frombuffer(b"".join(pool), dtype=np.uint8)
+            off = np.zeros(len(pool) + 1, dtype=np.uint64)
+            if len(pool):
+                off[1:] = np.cumsum([len(s) for s in pool], dtype=np.uint64)
+        return data, off, max(int(off.size) - 1, 0)
+
+    def _sw_call(self, call, n: int, cap: int):
+        """the buffer from the caller's bound on the operations, one retry on n_ops_out if the bound was not known"""
+        need = C.c_uint64()
+        cigar_off, offset = np.zeros(n + 1, dtype=np.uint64), np.zeros(n, dtype=np.int32)
+        for _ in range(2):
+            cigar = np.zeros(max(cap, 1), dtype=np.uint32)
+            rc = call(_vp(cigar), cap, _vp(cigar_off), _vp(offset), C.byref(need))
+            if rc == 0 or int(need.value) <= cap:
+                break
+            cap = int(need.value)
+        self._check(rc)
+        return cigar_off, cigar[:int(need.value)].copy(), offset
+
+    def sw_align(self, refs, alts, ref_of, alt_of, params, strategy: int):
+        """elp_sw_align: runSmithWaterman(refs[ref_of[k]], alts[alt_of[k]], *params, strategy) for every k.  Pools: a list of bytes, or
+        (bytes, off).  Returns (cigar_off, cigar, offset): problem k's CIGAR is cigar[cigar_off[k]:cigar_off[k + 1]] in BAM's len << 4 | op."""
+        a, a_off, n_a = self._sw_pool(refs)
+        b, b_off, n_b = self._sw_pool(alts)
+        ref_of = np.ascontiguousarray(ref_of, dtype=np.uint32)
+        alt_of = np.ascontiguousarray(alt_of, dtype=np.uint32)
+        n = int(ref_of.size)
+        assert alt_of.size == n
+        cap = 0
+        if n and n_a and n_b and int(ref_of.max()) < n_a and int(alt_of.max()) < n_b:  # len_ref + len_alt + 2 operations at most per problem
+            cap = int(((a_off[1:] - a_off[:-1])[ref_of] + (b_off[1:] - b_off[:-1])[alt_of] + np.uint64(2)).sum())
+        m, x, go, ge = (int(v) for v in params)
+        return self._sw_call(lambda cig, cap_, coff, off, need: self.L.elp_sw_align(self.h, n_a, _vp(a), _vp(a_off), n_b, _vp(b), _vp(b_off), n, _vp(ref_of), _vp(alt_of),
+                                                                                     m, x, go, ge, int(strategy), cig, cap_, coff, off, need), n, cap)
+
+    def sw_align_reads(self, refs, ref_of, read_idx, params, strategy: int):
+        """elp_sw_align_reads: the alternates are SEQ.AsString() of the staged records read_idx (staged with stage_bam / _bgzf / _sam)"""
+        a, a_off, n_a = self._sw_pool(refs)
+        ref_of = np.ascontiguousarray(ref_of, dtype=np.uint32)
+        read_idx = np.ascontiguousarray(read_idx, dtype=np.uint32)
+        n = int(ref_of.size)
+        assert read_idx.size == n
+        m, x, go, ge = (int(v) for v in params)
+        return self._sw_call(lambda cig, cap_, coff, off, need: self.L.elp_sw_align_reads(self.h, n_a, _vp(a), _vp(a_off), n, _vp(ref_of), _vp(read_idx), m, x, go, ge,
+                                                                                           int(strategy), cig, cap_, coff, off, need), n, 8 * n)
+
     # ---- SAM text out (include/elprep_hip.h: FormatAlignment on the device)
     def _n_ref_in_force(self) -> int:
         n_ref = getattr(self, "_n_ref_now", None)  # (set by replace_reference_dictionary, until reset())

@@ -674,6 +674,46 @@ int elp_get_qual(elp_ctx *ctx, uint8_t *qual_out /* qual_bytes, staging order an
  * position in CleanSam."), ELP_ERR_UNSUPPORTED for a clip length that does not fit the 28 bits of a BAM CIGAR field. */
 int elp_clean_sam(elp_ctx *ctx, uint64_t *n_clipped_out);
 
+/* ---- the HaplotypeCaller's Smith-Waterman: runSmithWaterman (filters/sw.go:110-316; csrc/sw.hip, sw_core.hpp, sw_plan.hpp) ----
+ * The one kernel of the HaplotypeCaller whose arithmetic is all int32.  The reference calls it once per read of every assembly region
+ * against the read's best haplotype (filters/realign.go:310: 10, -15, -30, -5, softclip), per dangling tail or head
+ * (filters/assemble-reads.go:1042,1152: 25, -50, -110, -6, leadingIndel) and per haplotype through calculateCigar (filters/sw.go:401: 200,
+ * -150, -260, -11, softclip).  A batch is a pool of reference sequences, a pool of alternate sequences - bytes as the Go strings hold
+ * them, sequence s of a pool = pool[off[s] .. off[s + 1]) - and n problems (ref_of[k], alt_of[k]); both forms are flat (cgo: no
+ * pointers to pointers).  elp_sw_align_reads takes its alternates from staged records: problem k's is SEQ.AsString() of staged record
+ * read_idx[k] (any order, repeats allowed), the nibbles decoded by "=ACMGRSVTWYHKDBN" - from the BAM records of elp_stage_bam /
+ * elp_stage_bgzf / elp_stage_sam, because column staging (elp_stage) keeps A, C, G, T and "other" only: ELP_ERR_ARG there.
+ *   Result, exactly what runSmithWaterman returns: problem k's CIGAR is cigar_out[cigar_off_out[k] .. cigar_off_out[k + 1]) in BAM's
+ * len << 4 | op words as elp_batch.cigar holds them (only M, I, D and S occur), its alignment offset offset_out[k] (negative offsets
+ * included: `ignore` returns p1 - p2).  *n_ops_out = all operations.  A CIGAR never has more than len(ref) + len(alt) + 2 operations
+ * (the traceback makes at most len(ref) + len(alt) steps, each at most one segment, the tails add two, and a leading S takes at least one step away), so a buffer of the sum of
+ * that over the problems always suffices; if *n_ops_out exceeds cigar_cap the call returns ELP_ERR_ARG, *n_ops_out holds the need and
+ * the output arrays are unspecified.  n == 0 succeeds with cigar_off_out[0] = 0.
+ *   What is reproduced (sw.go line by line): the exact-substring shortcut of softclip and ignore (:113-118) - the LAST occurrence of the
+ * raw alternate in the reference under fasta.ToUpperAndN (lastIndex, :96-108: acgtn / ACGTN -> ACGTN, the other IUPAC letters -> N); the
+ * recurrence on raw bytes with bestGap += gapExtend in front of the strict test, diagonal if >= both, else right if >= down, else down,
+ * interior cells clamped at -100000000 and the first row and column of indel / leadingIndel not clamped (:141-210); the end search
+ * (:212-238); the traceback, the three strategy tails, the reversal and the clean-up loop as it stands, which does not compare the
+ * element in front of a removed zero-length one with what moves up (:240-315).
+ *   Stated limits (ELP_ERR_UNSUPPORTED): a sequence (one that a problem uses) longer than 4095 bytes - a gap length then fits the int16 the
+ * backtrack is stored in -, a parameter whose absolute value exceeds 65535, 2^31 or more problems.  With both limits no int32 of the
+ * reference can wrap: bestGap starts at MinInt32 / 2 = -1073741824 and falls by at most 4095 * 65535 = 268365825 to -1342107649 >
+ * MinInt32 = -2147483648; a score is a sum of at most 8190 parameters, within +-536731650 < 2^30.
+ *   ELP_ERR_ARG: a NULL context or output pointer, strategy outside 0 .. 3, offsets that do not start at 0 or decrease, an index outside
+ * its pool, read_idx[k] >= elp_num_records, and an EMPTY sequence that a problem uses (the reference's answer there - a 0M, or an
+ * out-of-range index - is an accident of its loops; it is refused, not reproduced).
+ *   The call runs on the context's stream, reads the staged records and nothing else of the context, changes no staged or derived
+ * state, and uses the context's scratch (sw_plan.hpp lists the slots); as every call on one context it must not overlap another.
+ * The problems that miss the shortcut run in chunks of at most 1 GiB of scratch (elp_set_tuning "sw_scratch_bytes"). */
+typedef enum elp_sw_strategy { ELP_SW_SOFTCLIP = 0, ELP_SW_INDEL = 1, ELP_SW_LEADING_INDEL = 2, ELP_SW_IGNORE = 3 } elp_sw_strategy; /* sw.go:31-36 */
+int elp_sw_align(elp_ctx *ctx, uint64_t n_a, const uint8_t *a, const uint64_t *a_off /* n_a + 1 */, uint64_t n_b, const uint8_t *b, const uint64_t *b_off /* n_b + 1 */,
+                 uint64_t n, const uint32_t *ref_of /* n, index into a */, const uint32_t *alt_of /* n, index into b */, int32_t match, int32_t mismatch, int32_t gap_open,
+                 int32_t gap_extend, int strategy, uint32_t *cigar_out, uint64_t cigar_cap /* in ops */, uint64_t *cigar_off_out /* n + 1 */, int32_t *offset_out /* n */,
+                 uint64_t *n_ops_out);
+int elp_sw_align_reads(elp_ctx *ctx, uint64_t n_a, const uint8_t *a, const uint64_t *a_off, uint64_t n, const uint32_t *ref_of, const uint32_t *read_idx /* n staging indices */,
+                       int32_t match, int32_t mismatch, int32_t gap_open, int32_t gap_extend, int strategy, uint32_t *cigar_out, uint64_t cigar_cap, uint64_t *cigar_off_out,
+                       int32_t *offset_out, uint64_t *n_ops_out);
+
 /* Measurement and test harness entry points of the same library (snapshot / rollback of the mutable columns, pinned kernel choices, per-kernel
  * timing) are declared in elprep_hip_debug.h: they are not part of the reference's interface and a drop-in host does not need them. */
 

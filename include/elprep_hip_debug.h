@@ -40,6 +40,8 @@ int elp_rollback(elp_ctx *ctx);
  *   "bgzf_stored"      1: elp_emit_sorted_bgzf frames stored DEFLATE blocks (BTYPE 00) instead of compressing
  *   "emit_pass"        > 0: at most this many records per pass of the BAM / BGZF emitters (default 2 M, less for long records)
  *   "sam_pass"         > 0: at most this many lines per write pass of elp_stage_sam (default: all lines of a piece of text at once)
+ *   "sw_scratch_bytes" > 0: elp_sw_align / elp_sw_align_reads run the problems that miss the shortcut in chunks of at most this many
+ *                      bytes of scratch (default 1 GiB; a single problem that needs more still runs, alone); negative values are refused
  *   "bgzf_piece"       inflated bytes per record-scan pass of elp_stage_bgzf (default 1 GiB)
  *   "bgzf_inflate_piece"  inflated bytes whose blocks one launch of the decoder takes (default 2 GiB; the scan passes of
  *                      "bgzf_piece" bytes run inside it; token scratch: 171 KB per 64 KB block)
